@@ -8,8 +8,16 @@ RCCL all-gather across ranks. Weak scaling: policies_per_gen = 1280 per GPU
 
 Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W                 # single GPU
+  python bench.py ... --dump-outputs DIR    # + last timed step's outputs (.npy)
+  python bench.py ... --full                # + per-phase breakdown in the JSON
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N ...             # one rank/GPU
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K generations, print one JSON line. With the same arguments every input
+(noise table, initial weights, env matrices, per-generation draws) is
+identical from run to run, so --dump-outputs of two builds compare output
+for output.
 
 A "step" is one ES generation. Data is synthetic (seeded latent-dynamics env
 of Humanoid-v2's 376-obs/17-action shape; no physics engine or datasets exist
@@ -28,6 +36,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -66,7 +75,19 @@ def main():
                    help="rollout launch shape: per-step graph-replayed grid, or "
                         "one whole-episode launch per generation (blocks drift; "
                         "phases overlap chip-wide)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "generation returned (fitnesses, noise indices, "
+                        "shaped ranks, noiseless evaluation, observation "
+                        "statistics, updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure: adds the "
+                        "last generation's per-phase wall-time breakdown to "
+                        "the result line (off by default; a plain run only "
+                        "sets up, warms up, times the steps and reports)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
 
     from es_pytorch_amd.config import AttrDict
     from es_pytorch_amd.core.engine import GpuEngine
@@ -107,6 +128,12 @@ def main():
     # fixed-horizon synthetic rollouts: every counted env step is a fully
     # computed batched forward + dynamics step (stable, honest throughput)
     env_kwargs = dict(max_steps=args.max_steps, terminate_on_fall=False)
+    if os.environ.get("PYTHONHASHSEED", "random") == "random":
+        # the env's default matrix seed goes through hash(name), salted per
+        # process: pin it so every run (and every rank) sees the same
+        # dynamics. An interpreter with a pinned hash seed already does, and
+        # keeps the matrices it always had.
+        env_kwargs["matrix_seed"] = 0xE5 + zlib.crc32(args.env.encode()) % 100000
     env = make_batched(cfg.env.name, B, device, **env_kwargs)
     nn = FeedForward(cfg.policy.layer_sizes, torch.nn.Tanh(), env, cfg.policy.ac_std,
                      cfg.policy.ob_clip)
@@ -148,8 +175,9 @@ def main():
         torch.cuda.synchronize(device)
     t0 = time.perf_counter()
     steps_done = 0
+    last = None
     for _ in range(args.steps):
-        tr, _ = engine.step(ranker) if use_cuda else (engine.step(ranker), None)
+        last = engine.step(ranker)
         if args.objective == "nsr" and use_cuda:
             # on-device archive growth inside the timed region (reference
             # nsra.py:130-135): ONE 2-float broadcast + device cdist re-score
@@ -170,6 +198,11 @@ def main():
     # env_steps from engine are already whole-job (allreduced per gen)
     env_steps_per_sec = steps_done / elapsed
     gens_per_sec = args.steps / elapsed
+
+    if args.dump_outputs and comm.rank == 0:
+        # after the clock stopped: every rank holds identical outputs
+        # (redundant ranking/update), so rank 0's copy is the job's
+        _dump_outputs(args.dump_outputs, last, ranker, policy)
 
     if comm.rank == 0:
         out = {
@@ -203,8 +236,38 @@ def main():
                 "n_params": len(policy),
             },
         }
+        if args.full:
+            out["config"]["last_step_timings"] = {
+                k: round(float(v), 6) for k, v in engine.timings.items()}
         print(json.dumps(out))
     return 0
+
+
+def _dump_outputs(folder, last, ranker, policy):
+    """Write what a caller of the timed path holds after its last step: the
+    (noiseless result, generation ObStat) pair engine.step returned, the
+    ranker it filled and the parameters it updated — one .npy each, fp64
+    except the fp32 parameters (well under 1 MB in all at flagship size)."""
+    os.makedirs(folder, exist_ok=True)
+    arrays = {
+        "fits_pos": np.asarray(ranker.fits_pos, dtype=np.float64),
+        "fits_neg": np.asarray(ranker.fits_neg, dtype=np.float64),
+        "noise_inds": np.asarray(ranker.noise_inds, dtype=np.float64),
+        "ranked_fits": np.asarray(ranker.ranked_fits, dtype=np.float64),
+        "flat_params": np.asarray(policy.flat_params, dtype=np.float32),
+    }
+    if last is not None:  # the CPU stand-in returns nothing
+        noiseless, obstat = last
+        arrays.update({
+            "noiseless_result": np.asarray(noiseless.result, dtype=np.float64),
+            "noiseless_behaviour": np.asarray(noiseless.behaviour, dtype=np.float64),
+            "env_steps": np.asarray([noiseless.steps], dtype=np.float64),
+            "obstat_sum": np.asarray(obstat.sum, dtype=np.float64),
+            "obstat_sumsq": np.asarray(obstat.sumsq, dtype=np.float64),
+            "obstat_count": np.asarray([obstat.count], dtype=np.float64),
+        })
+    for name, arr in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), arr)
 
 
 class _CpuRefEngine:

@@ -49,7 +49,11 @@ LOCO_SHAPES = {
 class SyntheticLocomotion(BatchedEnv):
     def __init__(self, name: str, batch: int, device="cpu", max_steps: int = 1000,
                  terminate_on_fall: bool = True, env_seed: int = 0xE5, dt: float = 0.05,
-                 goal_conditioned: bool = False):
+                 goal_conditioned: bool = False, matrix_seed: Optional[int] = None):
+        # matrix_seed: exact generator seed of the fixed matrices. The
+        # default (None) derives it from env_seed and hash(name), and str
+        # hashes are salted per process unless PYTHONHASHSEED pins them —
+        # callers that need the same matrices in every process pass it
         super().__init__(batch, torch.device(device))
         base = name.replace("Flagrun", "") if goal_conditioned else name
         ob_dim, ac_dim = LOCO_SHAPES[name]
@@ -61,7 +65,9 @@ class SyntheticLocomotion(BatchedEnv):
         self.observation_space = Box(-np.inf, np.inf, (ob_dim,))
         self.action_space = Box(-1.0, 1.0, (ac_dim,))
 
-        g = torch.Generator(device="cpu").manual_seed(env_seed + abs(hash(base)) % 100000)
+        if matrix_seed is None:
+            matrix_seed = env_seed + abs(hash(base)) % 100000
+        g = torch.Generator(device="cpu").manual_seed(int(matrix_seed))
         S, A = self.sdim, ac_dim
         d = self.device
         # the state-transition matrix is held at bf16 precision (stored

@@ -125,8 +125,11 @@ def test_simple_example_torchrun_world2(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            "--nproc-per-node", "2", "--standalone", "--local-addr", "127.0.0.1",
            os.path.join(ROOT, "examples", "simple_example.py"), str(cfg_path)]
+    # gloo named explicitly: on a machine with a visible GPU the default
+    # transport is RCCL, which rejects two ranks sharing one device
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
-                       cwd=str(tmp_path), env=dict(os.environ, PYTHONPATH=ROOT))
+                       cwd=str(tmp_path),
+                       env=dict(os.environ, PYTHONPATH=ROOT, ES_COMM_BACKEND="gloo"))
     assert r.returncode == 0, r.stderr[-3000:]
     assert "avg fitness" in r.stdout
 
