@@ -69,6 +69,20 @@ def _torch_mlp_ref(obs, weights_bf16, dims, obmean, obstd, ob_clip):
     return torch.stack(out)
 
 
+def _assert_mlp_matches_oracle64(actions, obs, weights, dims, obmean, obstd, ob_clip):
+    """|kernel - float64 oracle| <= 16 x the float32 error of the same forward
+    (tests/oracle64.py) — about a thousand times tighter than the torch
+    reference above allows."""
+    from tests.oracle64 import (ERR_FACTOR, bf16_bits_to_f64, fp32_error_scale, max_ratio,
+                                policy_actions)
+    wvals = bf16_bits_to_f64(weights.view(torch.int16).cpu().numpy().view(np.uint16))
+    y64, e32 = fp32_error_scale(policy_actions, dims=dims, weight_rows=wvals,
+                                obs=obs.cpu().numpy(), obmean=obmean.cpu().numpy(),
+                                obstd=obstd.cpu().numpy(), ob_clip=ob_clip)
+    r = max_ratio(actions.cpu().numpy(), y64, e32)
+    assert r <= ERR_FACTOR, (r, e32)
+
+
 def test_mlp_fwd_kernel(dev):
     from es_pytorch_amd import ops
     torch.manual_seed(0)
@@ -90,6 +104,7 @@ def test_mlp_fwd_kernel(dev):
     ref = _torch_mlp_ref(obs, weights, dims, obmean, obstd, 5.0)
     assert torch.allclose(actions, ref, atol=2e-2, rtol=2e-2), \
         (actions - ref).abs().max().item()
+    _assert_mlp_matches_oracle64(actions, obs, weights, dims, obmean, obstd, 5.0)
 
 
 def test_mlp_fwd_odd_output_dim(dev):
@@ -113,6 +128,7 @@ def test_mlp_fwd_odd_output_dim(dev):
     torch.cuda.synchronize()
     ref = _torch_mlp_ref(obs, weights, dims, obmean, obstd, 5.0)
     assert torch.allclose(actions, ref, atol=2e-2, rtol=2e-2)
+    _assert_mlp_matches_oracle64(actions, obs, weights, dims, obmean, obstd, 5.0)
 
 
 def test_mlp_fwd_action_noise_statistics(dev):
@@ -166,6 +182,10 @@ def test_grad_gather_kernel(dev):
     rows = torch.stack([table[o:o + n] for o in offs.cpu()])
     expect = fits.cpu() @ rows.cpu()
     assert torch.allclose(g.cpu(), expect, atol=1e-3, rtol=1e-4)
+    from tests.oracle64 import ERR_FACTOR, fp32_error_scale, grad_gather, max_ratio
+    y64, e32 = fp32_error_scale(grad_gather, table.cpu().numpy(), offs.cpu().numpy(),
+                                fits.cpu().numpy(), n)
+    assert max_ratio(g.cpu().numpy(), y64, e32) <= ERR_FACTOR
 
 
 def test_adam_kernel_matches_numpy(dev):
