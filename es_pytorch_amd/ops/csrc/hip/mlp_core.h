@@ -17,6 +17,66 @@
 #define ES_MAXL 8
 #define ES_MAXDIM 2048
 
+// ES_HEAD_BATCH: the scalar-layer walks (the 256->17 action head runs here)
+// issue ES_HEAD_BT rows' weight loads into registers before the first FMA
+// of the batch, instead of one load + s_waitcnt vmcnt(0) per row (what hipcc
+// emits for the plain loop: every trip a fully exposed memory round trip on
+// a path all waves execute, with a barrier behind it). The flagship head is
+// 18/17 trips per thread -> 3 waits instead of 18. FMA order (ascending row)
+// and operands are unchanged -> bitwise-same results. 0 restores the old
+// loops.
+#ifndef ES_HEAD_BATCH
+#define ES_HEAD_BATCH 1
+#endif
+#define ES_HEAD_BT 8
+
+// Guarded drain of es_walk_batched: R rows every thread owns, then the one
+// row only some threads own. All R + 1 loads issue ahead of the first FMA;
+// the conditional row's load is clamped to row 0 where the thread has none.
+template <int R, typename W, typename LD, typename FMA>
+__device__ __forceinline__ void es_walk_drain(int r0, int st, int I, LD ld, FMA fma) {
+  W w[R + 1];
+  const int rl = r0 + R * st;
+  const bool ok = rl < I;
+#pragma unroll
+  for (int u = 0; u < R; ++u) w[u] = ld(r0 + u * st);
+  w[R] = ld(ok ? rl : 0);
+#pragma unroll
+  for (int u = 0; u < R; ++u) fma(w[u], r0 + u * st);
+  if (ok) fma(w[R], rl);
+}
+
+// Batched strided row walk r = i0, i0 + st, ... < I for the scalar layers.
+// st and I are block-uniform and 0 <= i0 < st, so with T = ceil(I / st) every
+// thread owns trips 0..T-2 and only trip T-1 depends on the thread. The
+// T-1 common trips run in straight-line batches of ES_HEAD_BT loads followed
+// by ES_HEAD_BT FMAs (uniform control flow, nothing for the compiler to sink
+// behind a wait); the remainder and the conditional trip drain together.
+template <typename W, typename LD, typename FMA>
+__device__ __forceinline__ void es_walk_batched(int i0, int st, int I, LD ld, FMA fma) {
+  const int T = (I + st - 1) / st;
+  int t = 0;
+  for (; t + ES_HEAD_BT <= T - 1; t += ES_HEAD_BT) {
+    W w[ES_HEAD_BT];
+#pragma unroll
+    for (int u = 0; u < ES_HEAD_BT; ++u) w[u] = ld(i0 + (t + u) * st);
+#pragma unroll
+    for (int u = 0; u < ES_HEAD_BT; ++u) fma(w[u], i0 + (t + u) * st);
+  }
+  const int r0 = i0 + t * st;
+  static_assert(ES_HEAD_BT == 8, "drain switch covers remainders 0..7");
+  switch (T - 1 - t) {
+    case 0: es_walk_drain<0, W>(r0, st, I, ld, fma); break;
+    case 1: es_walk_drain<1, W>(r0, st, I, ld, fma); break;
+    case 2: es_walk_drain<2, W>(r0, st, I, ld, fma); break;
+    case 3: es_walk_drain<3, W>(r0, st, I, ld, fma); break;
+    case 4: es_walk_drain<4, W>(r0, st, I, ld, fma); break;
+    case 5: es_walk_drain<5, W>(r0, st, I, ld, fma); break;
+    case 6: es_walk_drain<6, W>(r0, st, I, ld, fma); break;
+    default: es_walk_drain<7, W>(r0, st, I, ld, fma); break;
+  }
+}
+
 struct MlpShape {
   int n_layers;
   int dims[ES_MAXL + 1];
@@ -147,6 +207,11 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
         const int oi = tid % O, ip = tid / O;
         float acc = 0.0f;
         if (ip < PART) {
+#if ES_HEAD_BATCH
+          es_walk_batched<uint16_t>(
+              ip, PART, I, [&](int r) { return Wt[(int64_t)r * O + oi]; },
+              [&](uint16_t w, int r) { acc = fmaf(bf2f(w), x[r], acc); });
+#else
           int i = ip;
           const int step4 = PART * 4;
           for (; i + 3 * PART < I; i += step4) {
@@ -160,6 +225,7 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
             acc = fmaf(w3, x[i + 3 * PART], acc);
           }
           for (; i < I; i += PART) acc = fmaf(bf2f(Wt[(int64_t)i * O + oi]), x[i], acc);
+#endif
           partial[ip * O + oi] = acc;
         }
         __syncthreads();
@@ -171,6 +237,11 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
       } else {
         for (int o = tid; o < O; o += nthreads) {
           float acc = bf2f(Bs[o]);
+#if ES_HEAD_BATCH
+          es_walk_batched<uint16_t>(
+              0, 1, I, [&](int r) { return Wt[(int64_t)r * O + o]; },
+              [&](uint16_t w, int r) { acc = fmaf(bf2f(w), x[r], acc); });
+#else
           int i = 0;
           for (; i + 3 < I; i += 4) {
             const float w0 = bf2f(Wt[(int64_t)i * O + o]);
@@ -183,6 +254,7 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
             acc = fmaf(w3, x[i + 3], acc);
           }
           for (; i < I; ++i) acc = fmaf(bf2f(Wt[(int64_t)i * O + o]), x[i], acc);
+#endif
           y[o] = do_act ? tanhf(acc) : acc;
         }
       }
@@ -194,6 +266,10 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
   }
   return x;
 }
+
+// one row's (theta, sigma*eps) scalar pair as loaded by the batched walks
+struct EsTE8 { uint16_t t; uint8_t e; };
+struct EsTE16 { uint16_t t; uint16_t e; };
 
 // theta octet (bf16) +- decoded fp8 eps octet, FMA'd into both members
 __device__ __forceinline__ void bf8e_fma_pair(uint4 t, const float* e8, float xp,
@@ -364,12 +440,25 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         const int oi = tid % O, ip = tid / O;
         float accp = 0.0f, accm = 0.0f;
         if (ip < PART) {
+#if ES_HEAD_BATCH
+          es_walk_batched<EsTE8>(
+              ip, PART, I,
+              [&](int r) {
+                return EsTE8{Tt[(int64_t)r * O + oi], Et8[(int64_t)r * O + oi]};
+              },
+              [&](EsTE8 w, int r) {
+                const float tw = bf2f(w.t), ew = fp8_byte(w.e);
+                accp = fmaf(tw + ew, xp[r], accp);
+                accm = fmaf(tw - ew, xm[r], accm);
+              });
+#else
           for (int i = ip; i < I; i += PART) {
             const float tw = bf2f(Tt[(int64_t)i * O + oi]);
             const float ew = fp8_byte(Et8[(int64_t)i * O + oi]);
             accp = fmaf(tw + ew, xp[i], accp);
             accm = fmaf(tw - ew, xm[i], accm);
           }
+#endif
           partial[ip * O + oi] = accp;
           partm[ip * O + oi] = accm;
         }
@@ -388,12 +477,25 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         for (int o = tid; o < O; o += nthreads) {
           const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
           float accp = tB + eB, accm = tB - eB;
+#if ES_HEAD_BATCH
+          es_walk_batched<EsTE8>(
+              0, 1, I,
+              [&](int r) {
+                return EsTE8{Tt[(int64_t)r * O + o], Et8[(int64_t)r * O + o]};
+              },
+              [&](EsTE8 w, int r) {
+                const float tw = bf2f(w.t), ew = fp8_byte(w.e);
+                accp = fmaf(tw + ew, xp[r], accp);
+                accm = fmaf(tw - ew, xm[r], accm);
+              });
+#else
           for (int i = 0; i < I; ++i) {
             const float tw = bf2f(Tt[(int64_t)i * O + o]);
             const float ew = fp8_byte(Et8[(int64_t)i * O + o]);
             accp = fmaf(tw + ew, xp[i], accp);
             accm = fmaf(tw - ew, xm[i], accm);
           }
+#endif
           yp[o] = do_act ? tanhf(accp) : accp;
           ym[o] = do_act ? tanhf(accm) : accm;
         }
@@ -538,12 +640,25 @@ __device__ __forceinline__ void mlp_layers_pair(
         const int oi = tid % O, ip = tid / O;
         float accp = 0.0f, accm = 0.0f;
         if (ip < PART) {
+#if ES_HEAD_BATCH
+          es_walk_batched<EsTE16>(
+              ip, PART, I,
+              [&](int r) {
+                return EsTE16{Tt[(int64_t)r * O + oi], Et[(int64_t)r * O + oi]};
+              },
+              [&](EsTE16 w, int r) {
+                const float tw = bf2f(w.t), ew = bf2f(w.e);
+                accp = fmaf(tw + ew, xp[r], accp);
+                accm = fmaf(tw - ew, xm[r], accm);
+              });
+#else
           for (int i = ip; i < I; i += PART) {
             const float tw = bf2f(Tt[(int64_t)i * O + oi]);
             const float ew = bf2f(Et[(int64_t)i * O + oi]);
             accp = fmaf(tw + ew, xp[i], accp);
             accm = fmaf(tw - ew, xm[i], accm);
           }
+#endif
           partial[ip * O + oi] = accp;
           partm[ip * O + oi] = accm;
         }
@@ -562,12 +677,25 @@ __device__ __forceinline__ void mlp_layers_pair(
         for (int o = tid; o < O; o += nthreads) {
           const float tB = bf2f(TBs[o]), eB = bf2f(EBs[o]);
           float accp = tB + eB, accm = tB - eB;
+#if ES_HEAD_BATCH
+          es_walk_batched<EsTE16>(
+              0, 1, I,
+              [&](int r) {
+                return EsTE16{Tt[(int64_t)r * O + o], Et[(int64_t)r * O + o]};
+              },
+              [&](EsTE16 w, int r) {
+                const float tw = bf2f(w.t), ew = bf2f(w.e);
+                accp = fmaf(tw + ew, xp[r], accp);
+                accm = fmaf(tw - ew, xm[r], accm);
+              });
+#else
           for (int i = 0; i < I; ++i) {
             const float tw = bf2f(Tt[(int64_t)i * O + o]);
             const float ew = bf2f(Et[(int64_t)i * O + o]);
             accp = fmaf(tw + ew, xp[i], accp);
             accm = fmaf(tw - ew, xm[i], accm);
           }
+#endif
           yp[o] = do_act ? tanhf(accp) : accp;
           ym[o] = do_act ? tanhf(accm) : accm;
         }

@@ -72,6 +72,40 @@ __device__ __forceinline__ void loco_build_obs(
   }
 }
 
+// ES_PAIR_OBS: one obs pass for both members of a pair — obmean/obstd are
+// loaded once and both members' state loads issue together (0: two
+// one-member passes). Same per-member arithmetic, division included.
+#ifndef ES_PAIR_OBS
+#define ES_PAIR_OBS 1
+#endif
+__device__ __forceinline__ void loco_build_obs_pair(
+    const LocoArgs& la, const LocoPtrs& P, int bp, int bm, float* bufAp, float* bufAm,
+    float* rawsP, float* rawsM, int tid, int nth) {
+#if ES_PAIR_OBS
+  const int S = la.S;
+  const float* sp = P.s_glob + (int64_t)bp * S;
+  const float* sm = P.s_glob + (int64_t)bm * S;
+  for (int i = tid; i < S; i += nth) {
+    const float vp = sp[i], vm = sm[i];
+    const float mean = P.obmean[i], sd = P.obstd[i];
+    rawsP[i] = vp;
+    rawsM[i] = vm;
+    bufAp[i] = fclampf((vp - mean) / sd, -la.ob_clip, la.ob_clip);
+    bufAm[i] = fclampf((vm - mean) / sd, -la.ob_clip, la.ob_clip);
+  }
+  if (la.goal && tid < 2) {
+    const float relp = (P.goal[(int64_t)bp * 2 + tid] - P.pos[(int64_t)bp * 3 + tid]) * 0.1f;
+    const float relm = (P.goal[(int64_t)bm * 2 + tid] - P.pos[(int64_t)bm * 3 + tid]) * 0.1f;
+    const float mean = P.obmean[S + tid], sd = P.obstd[S + tid];
+    bufAp[S + tid] = fclampf((relp - mean) / sd, -la.ob_clip, la.ob_clip);
+    bufAm[S + tid] = fclampf((relm - mean) / sd, -la.ob_clip, la.ob_clip);
+  }
+#else
+  loco_build_obs(la, P, bp, bufAp, rawsP, tid, nth);
+  loco_build_obs(la, P, bm, bufAm, rawsM, tid, nth);
+#endif
+}
+
 // ---- net output -> clamped env action for slot b (modes 0/1/2/3) ---------
 __device__ __forceinline__ void loco_decode_action(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P, int b, uint64_t salt,
@@ -190,112 +224,251 @@ __device__ __forceinline__ void loco_dyn_partials(
   __syncthreads();
 }
 
-// Dynamics output sweep + fused epilogue for ONE member. The sweep that
-// materializes s' also accumulates the reward/behaviour reduction partials
-// AND the per-member obs statistics in the same pass (one s'-sweep instead
-// of three, and wave shuffles replace the 8-barrier LDS reduction tree).
-// When S % 8 == 0 the A-matvec partials must already be in `partial`
-// (loco_dyn_partials); otherwise the scalar fallback reads Am directly.
-__device__ __forceinline__ void loco_dyn_finish(
-    const LocoArgs& la, const LocoPtrs& P, int b, const float* raws,
-    const float* abuf, float* partial, int tid, int nth) {
+// ES_DYN_BM_BT: action-term batch depth. The B column of an output is loaded
+// ES_DYN_BM_BT rows at a time into registers before the ordered fmaf chain
+// consumes them (all of it up front when A <= 16; Humanoid's A = 17 takes
+// two batches instead of five serialized L2 round trips per output).
+#define ES_DYN_BM_BT 16
+
+// Scalars a member's bookkeeping lane needs. Their addresses depend on no
+// computed value, so the lane loads them BEFORE the output sweep instead of
+// on demand in the serial section while the rest of the block waits.
+struct LocoBook {
+  float px, py, gx, gy, rew_total, member_steps, ms0, ms1, mq0, mq1;
+};
+
+// Dynamics output sweep + fused epilogue for NM members in ONE pass. The
+// sweep that materializes s' also accumulates the reward/behaviour reduction
+// partials AND the per-member obs statistics (one s'-sweep instead of three,
+// and wave shuffles replace the 8-barrier LDS reduction tree). b0, the B
+// column and wv/wy/wh of an output are loaded once for all members; the
+// members share one shuffle reduction and one pair of barriers, and member
+// m's scalar bookkeeping runs in lane 0 of wave m, concurrently (needs
+// nth >= 64 * NM). Per-member arithmetic and summation order are those of a
+// one-member call, so NM only changes when loads issue and how often waves
+// wait. When S % 8 == 0 the A-matvec partials must already be in part[m]
+// (loco_dyn_partials*); otherwise the scalar fallback reads Am directly.
+template <int NM>
+__device__ __forceinline__ void loco_dyn_finish_n(
+    const LocoArgs& la, const LocoPtrs& P, const int* b, const float* const* raws,
+    const float* const* abuf, float* const* part, int tid, int nth) {
   const int S = la.S, A = la.A;
-  float* sb = P.s_glob + (int64_t)b * S;
-  const float w_alive = P.alive[b];  // pre-step alive, used as obstat weight
-  float p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-  float* ms = P.mo_sum + (int64_t)b * la.D;
-  float* mq = P.mo_sumsq + (int64_t)b * la.D;
+  float w_alive[NM];  // pre-step alive, used as obstat weight
+  float *sb[NM], *ms[NM], *mq[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) {
+    w_alive[m] = P.alive[b[m]];
+    sb[m] = P.s_glob + (int64_t)b[m] * S;
+    ms[m] = P.mo_sum + (int64_t)b[m] * la.D;
+    mq[m] = P.mo_sumsq + (int64_t)b[m] * la.D;
+  }
+  // bookkeeping lane of member m: lane 0 of wave m
+  const int wid = tid >> 6;
+  const bool book = (tid & 63) == 0 && wid < NM;
+  int bme = b[0];
+  float alive_me = w_alive[0];
+  float *part_me = part[0], *ms_me = ms[0], *mq_me = mq[0];
+#pragma unroll
+  for (int m = 1; m < NM; ++m)
+    if (wid == m) {
+      bme = b[m]; alive_me = w_alive[m];
+      part_me = part[m]; ms_me = ms[m]; mq_me = mq[m];
+    }
+  LocoBook bk = {};
+  if (book) {
+    bk.px = P.pos[(int64_t)bme * 3 + 0];
+    bk.py = P.pos[(int64_t)bme * 3 + 1];
+    bk.rew_total = P.rew_total[bme];
+    bk.member_steps = P.member_steps[bme];
+    if (la.goal) {
+      bk.gx = P.goal[(int64_t)bme * 2 + 0];
+      bk.gy = P.goal[(int64_t)bme * 2 + 1];
+      if (alive_me > 0.0f) {
+        bk.ms0 = ms_me[S]; bk.ms1 = ms_me[S + 1];
+        bk.mq0 = mq_me[S]; bk.mq1 = mq_me[S + 1];
+      }
+    }
+  }
+
+  float p0[NM], p1[NM], p2[NM], p3[NM];
+#pragma unroll
+  for (int m = 0; m < NM; ++m) p0[m] = p1[m] = p2[m] = p3[m] = 0.0f;
   {
     const bool oct8 = (S % 8 == 0);
     const int OCT = S >> 3;
     const int PART = oct8 ? nth / OCT : 0;
     for (int o = tid; o < S; o += nth) {
-      float p = P.b0[o];
+      // every load of this output whose address is known up front
+      const float b0o = P.b0[o], wvo = P.wv[o], wyo = P.wy[o], who = P.wh[o];
+      float mso[NM], mqo[NM];
+#pragma unroll
+      for (int m = 0; m < NM; ++m)
+        if (w_alive[m] > 0.0f) {
+          mso[m] = ms[m][o];
+          mqo[m] = mq[m][o];
+        }
+      float p[NM];
+#pragma unroll
+      for (int m = 0; m < NM; ++m) p[m] = b0o;
       if (oct8) {
         const int oo = o >> 3, j = o & 7;
-        for (int pp = 0; pp < PART; ++pp) p += partial[(pp * OCT + oo) * 8 + j];
+        for (int pp = 0; pp < PART; ++pp)
+#pragma unroll
+          for (int m = 0; m < NM; ++m) p[m] += part[m][(pp * OCT + oo) * 8 + j];
       } else {
-        for (int i = 0; i < S; ++i)
-          p = fmaf(raws[i], bf2f(P.Am[(int64_t)i * S + o]), p);
+        for (int i = 0; i < S; ++i) {
+          const float a = bf2f(P.Am[(int64_t)i * S + o]);
+#pragma unroll
+          for (int m = 0; m < NM; ++m) p[m] = fmaf(raws[m][i], a, p[m]);
+        }
       }
-      for (int k = 0; k < A; ++k) p = fmaf(abuf[k], P.Bm[(int64_t)k * S + o], p);
-      const float sn = (1.0f - la.leak) * raws[o] + la.leak * tanhf(p);
-      sb[o] = sn;
-      p0 = fmaf(sn, P.wv[o], p0);
-      p1 = fmaf(sn, P.wy[o], p1);
-      p2 = fmaf(sn, P.wh[o], p2);
-      if (w_alive > 0.0f) {
-        ms[o] += sn;
-        mq[o] += sn * sn;
+      // action term: batched B-column loads, ordered fmaf chain
+      const float* bcol = P.Bm + o;
+      int k0 = 0;
+      for (; k0 + ES_DYN_BM_BT <= A; k0 += ES_DYN_BM_BT) {
+        float bv[ES_DYN_BM_BT];
+#pragma unroll
+        for (int u = 0; u < ES_DYN_BM_BT; ++u) bv[u] = bcol[(int64_t)(k0 + u) * S];
+#pragma unroll
+        for (int u = 0; u < ES_DYN_BM_BT; ++u)
+#pragma unroll
+          for (int m = 0; m < NM; ++m) p[m] = fmaf(abuf[m][k0 + u], bv[u], p[m]);
+      }
+      if (k0 < A) {  // guarded drain (A is block-uniform)
+        float bv[ES_DYN_BM_BT];
+#pragma unroll
+        for (int u = 0; u < ES_DYN_BM_BT - 1; ++u)
+          if (k0 + u < A) bv[u] = bcol[(int64_t)(k0 + u) * S];
+#pragma unroll
+        for (int u = 0; u < ES_DYN_BM_BT - 1; ++u)
+          if (k0 + u < A) {
+#pragma unroll
+            for (int m = 0; m < NM; ++m) p[m] = fmaf(abuf[m][k0 + u], bv[u], p[m]);
+          }
+      }
+#pragma unroll
+      for (int m = 0; m < NM; ++m) {
+        const float sn = (1.0f - la.leak) * raws[m][o] + la.leak * tanhf(p[m]);
+        sb[m][o] = sn;
+        p0[m] = fmaf(sn, wvo, p0[m]);
+        p1[m] = fmaf(sn, wyo, p1[m]);
+        p2[m] = fmaf(sn, who, p2[m]);
+        if (w_alive[m] > 0.0f) {
+          ms[m][o] = mso[m] + sn;
+          mq[m][o] = mqo[m] + sn * sn;
+        }
       }
     }
     for (int j = tid; j < A; j += nth) {
-      p0 = fmaf(0.5f * abuf[j], P.wa[j], p0);
-      p3 = fmaf(abuf[j], abuf[j], p3);
+      const float waj = P.wa[j];
+#pragma unroll
+      for (int m = 0; m < NM; ++m) {
+        p0[m] = fmaf(0.5f * abuf[m][j], waj, p0[m]);
+        p3[m] = fmaf(abuf[m][j], abuf[m][j], p3[m]);
+      }
     }
   }
   // wave-level shuffle reduction, then one cross-wave pass through LDS
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    p0 += __shfl_down(p0, off);
-    p1 += __shfl_down(p1, off);
-    p2 += __shfl_down(p2, off);
-    p3 += __shfl_down(p3, off);
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      p0[m] += __shfl_down(p0[m], off);
+      p1[m] += __shfl_down(p1[m], off);
+      p2[m] += __shfl_down(p2[m], off);
+      p3[m] += __shfl_down(p3[m], off);
+    }
   }
-  __syncthreads();  // partial[] reuse after the dynamics matvec
+  __syncthreads();  // part[] reuse after the dynamics matvec
   if ((tid & 63) == 0) {
-    const int wid = tid >> 6;
-    partial[wid * 4 + 0] = p0;
-    partial[wid * 4 + 1] = p1;
-    partial[wid * 4 + 2] = p2;
-    partial[wid * 4 + 3] = p3;
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      part[m][wid * 4 + 0] = p0[m];
+      part[m][wid * 4 + 1] = p1[m];
+      part[m][wid * 4 + 2] = p2[m];
+      part[m][wid * 4 + 3] = p3[m];
+    }
   }
   __syncthreads();
 
-  // ---- scalar bookkeeping (thread 0) -------------------------------------
-  if (tid == 0) {
+  // ---- scalar bookkeeping (lane 0 of wave m for member m) ----------------
+  if (book) {
     const int nw = nth >> 6;
     float vfwd = 0, vy = 0, h = 0, asq = 0;
     for (int wdx = 0; wdx < nw; ++wdx) {
-      vfwd += partial[wdx * 4 + 0];
-      vy += partial[wdx * 4 + 1];
-      h += partial[wdx * 4 + 2];
-      asq += partial[wdx * 4 + 3];
+      vfwd += part_me[wdx * 4 + 0];
+      vy += part_me[wdx * 4 + 1];
+      h += part_me[wdx * 4 + 2];
+      asq += part_me[wdx * 4 + 3];
     }
-    const float alive_old = w_alive;
+    const float alive_old = alive_me;
     float rew;
     if (la.goal) {
-      const float rx = P.goal[(int64_t)b * 2 + 0] - P.pos[(int64_t)b * 3 + 0];
-      const float ry = P.goal[(int64_t)b * 2 + 1] - P.pos[(int64_t)b * 3 + 1];
+      const float rx = bk.gx - bk.px;
+      const float ry = bk.gy - bk.py;
       const float inv = 1.0f / (sqrtf(rx * rx + ry * ry) + 1e-6f);
       rew = vfwd * rx * inv + vy * ry * inv - la.ctrl * asq + la.alive_bonus;
     } else {
       rew = vfwd - la.ctrl * asq + la.alive_bonus;
     }
-    const float px = P.pos[(int64_t)b * 3 + 0] + la.dt * vfwd;
-    const float py = P.pos[(int64_t)b * 3 + 1] + la.dt * vy;
-    P.pos[(int64_t)b * 3 + 0] = px;
-    P.pos[(int64_t)b * 3 + 1] = py;
-    P.pos[(int64_t)b * 3 + 2] = h;
+    const float px = bk.px + la.dt * vfwd;
+    const float py = bk.py + la.dt * vy;
+    P.pos[(int64_t)bme * 3 + 0] = px;
+    P.pos[(int64_t)bme * 3 + 1] = py;
+    P.pos[(int64_t)bme * 3 + 2] = h;
     const float done = (la.terminate && h < la.fall_thr) ? 1.0f : 0.0f;
-    P.rew_total[b] += rew * alive_old;
-    P.member_steps[b] += alive_old;
+    P.rew_total[bme] = bk.rew_total + rew * alive_old;
+    P.member_steps[bme] = bk.member_steps + alive_old;
     if (alive_old > 0.0f) {
-      P.behv[(int64_t)b * 3 + 0] = px;
-      P.behv[(int64_t)b * 3 + 1] = py;
-      P.behv[(int64_t)b * 3 + 2] = h;
+      P.behv[(int64_t)bme * 3 + 0] = px;
+      P.behv[(int64_t)bme * 3 + 1] = py;
+      P.behv[(int64_t)bme * 3 + 2] = h;
     }
-    P.alive[b] = alive_old * (1.0f - done);
+    P.alive[bme] = alive_old * (1.0f - done);
+    // goal-relative obs dims of the per-member obs statistics (new pos)
+    if (la.goal && alive_old > 0.0f) {
+      const float rel0 = (bk.gx - px) * 0.1f;
+      const float rel1 = (bk.gy - py) * 0.1f;
+      ms_me[S] = bk.ms0 + rel0;
+      mq_me[S] = bk.mq0 + rel0 * rel0;
+      ms_me[S + 1] = bk.ms1 + rel1;
+      mq_me[S + 1] = bk.mq1 + rel1 * rel1;
+    }
   }
+  // next step of an episode kernel: alive/pos written above are read by
+  // other threads, and raws/part are rewritten
   __syncthreads();
+}
 
-  // goal-relative obs dims of the per-member obs statistics (needs new pos)
-  if (la.goal && w_alive > 0.0f && tid < 2) {
-    const float rel = (P.goal[(int64_t)b * 2 + tid] - P.pos[(int64_t)b * 3 + tid]) * 0.1f;
-    ms[S + tid] += rel;
-    mq[S + tid] += rel * rel;
-  }
-  __syncthreads();  // LDS reuse safety for the episode kernel's next step
+__device__ __forceinline__ void loco_dyn_finish(
+    const LocoArgs& la, const LocoPtrs& P, int b, const float* raws,
+    const float* abuf, float* partial, int tid, int nth) {
+  const int bs[1] = {b};
+  const float* const rs[1] = {raws};
+  const float* const as[1] = {abuf};
+  float* const ps[1] = {partial};
+  loco_dyn_finish_n<1>(la, P, bs, rs, as, ps, tid, nth);
+}
+
+// ES_PAIR_FINISH: one fused epilogue for both members of a pair (0: two
+// one-member calls, one after the other).
+#ifndef ES_PAIR_FINISH
+#define ES_PAIR_FINISH 1
+#endif
+__device__ __forceinline__ void loco_dyn_finish_pair(
+    const LocoArgs& la, const LocoPtrs& P, int bp, int bm, const float* rawsP,
+    const float* rawsM, const float* abufP, const float* abufM, float* partP,
+    float* partM, int tid, int nth) {
+#if ES_PAIR_FINISH
+  const int bs[2] = {bp, bm};
+  const float* const rs[2] = {rawsP, rawsM};
+  const float* const as[2] = {abufP, abufM};
+  float* const ps[2] = {partP, partM};
+  loco_dyn_finish_n<2>(la, P, bs, rs, as, ps, tid, nth);
+#else
+  loco_dyn_finish(la, P, bp, rawsP, abufP, partP, tid, nth);
+  loco_dyn_finish(la, P, bm, rawsM, abufM, partM, tid, nth);
+#endif
 }
 
 __device__ __forceinline__ void loco_step_body(
@@ -467,8 +640,9 @@ static int loco_launch_dyn(const LocoArgs& la, const LocoPtrs& P, const float* a
 // together off ONE HBM sigma*eps stream plus the L2-resident shared theta
 // stream (mlp_layers_pair, mlp_core.h) — the per-step HBM weight traffic
 // halves vs materialized per-member blobs. Dynamics shares each A octet
-// between the two members; the per-member epilogue is loco_dyn_finish
-// verbatim, so per-slot bookkeeping is identical to the fused step.
+// between the two members; the epilogue is the two-member instance of the
+// fused step's (loco_dyn_finish_n), same per-member arithmetic and order, so
+// per-slot bookkeeping is identical to the fused step.
 // Effective weights are bf16(theta) +- bf16(sigma*eps) (two roundings); with
 // sigma = 0 the trajectories are BITWISE-identical to es_loco_step.
 
@@ -566,8 +740,7 @@ __device__ __forceinline__ void loco_pair_step_body(
     float* rawsP, float* rawsM, float* abufP, float* abufM,
     float* partA = nullptr) {
   const int tid = threadIdx.x, nth = blockDim.x;
-  loco_build_obs(la, P, bp, bufAp, rawsP, tid, nth);
-  loco_build_obs(la, P, bm, bufAm, rawsM, tid, nth);
+  loco_build_obs_pair(la, P, bp, bm, bufAp, bufAm, rawsP, rawsM, tid, nth);
   __syncthreads();
   const bool early = ES_DYN_EARLY && partA != nullptr && la.S % 8 == 0;
   if (early)
@@ -587,8 +760,8 @@ __device__ __forceinline__ void loco_pair_step_body(
   if (!early && la.S % 8 == 0)
     loco_dyn_partials_pair(P.Am, la.S, rawsP, rawsM, partial, partial + 2048,
                            tid, nth);
-  loco_dyn_finish(la, P, bp, rawsP, abufP, pd, tid, nth);
-  loco_dyn_finish(la, P, bm, rawsM, abufM, pd + 2048, tid, nth);
+  loco_dyn_finish_pair(la, P, bp, bm, rawsP, rawsM, abufP, abufM, pd, pd + 2048, tid,
+                       nth);
 }
 
 #define ES_LOCO_PAIR_CARVE()                                     \
