@@ -13,7 +13,9 @@ One rank = one GPU; per generation:
    halve; the gradient gather re-quantizes through the same converters so
    the update is estimator-exact), bf16 otherwise — that the pair rollout
    kernel combines into W+/- in registers (the noiseless evaluation of
-   ``es.py:48`` rides in the same batch either way);
+   ``es.py:48`` rides in the same batch either way); ``weights_dtype="fp32"``
+   materializes float32 member rows instead and runs the fp32-weight
+   forward (the reference's precision; no pair/fp8 variant);
 3. the rollout loop — fused HIP MLP forward over the whole population +
    batched env dynamics — is captured once into a hipGraph and replayed
    every generation (launch-overhead-free inner loop; SURVEY.md §7.2 step 2);
@@ -85,12 +87,39 @@ class GpuEngine:
                  fused: Optional[bool] = None, rollout_mode: str = "step",
                  split_dyn: Optional[bool] = None,
                  pair_rollout: Optional[bool] = None,
-                 eps_fp8: Optional[bool] = None):
+                 eps_fp8: Optional[bool] = None,
+                 weights_dtype: Optional[str] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
         # so no per-step rendezvous is required)
         self.rollout_mode = rollout_mode
+        # weights_dtype: "bf16" (default) evaluates the population at bf16
+        # weights; "fp32" materializes float32(theta + s*eps) member rows and
+        # runs the fp32-weight forward (reference precision: the reference
+        # computes flat_params + std * noise and the forward in fp32). fp32
+        # has no pair / fp8 / split variant: per-member fp32 rows only.
+        if weights_dtype is None:
+            weights_dtype = cfg.general.get("weights_dtype", "bf16")
+        if weights_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"weights_dtype must be 'bf16' or 'fp32', got "
+                             f"{weights_dtype!r}")
+        self.weights_dtype = weights_dtype
+        self.fp32 = weights_dtype == "fp32"
+        if self.fp32:
+            for flag, val in (("pair_rollout", pair_rollout), ("eps_fp8", eps_fp8),
+                              ("split_dyn", split_dyn)):
+                if val is True:
+                    raise ValueError(
+                        f"{flag}=True is not available with weights_dtype='fp32' "
+                        f"(the fp32 mode runs per-member fp32 rows only)")
+            ignored = [k for k in ("pair_rollout", "eps_fp8", "split_dyn")
+                       if bool(cfg.general.get(k, False))]
+            if ignored and comm.rank == 0:
+                import sys
+                print(f"[engine] weights_dtype=fp32: ignoring {', '.join(ignored)} "
+                      f"from the config (no fp32 variant)", file=sys.stderr)
+            pair_rollout = eps_fp8 = split_dyn = False
         # steps per launch in "step" mode: k>1 runs k consecutive env steps
         # per kernel launch (bounded block drift, fewer launch boundaries)
         self.steps_per_launch = int(cfg.general.get("steps_per_launch", 1) or 1)
@@ -165,9 +194,11 @@ class GpuEngine:
         self._load_optim_state()
 
         # member blob rows padded to 16 B so the forward kernel's uint4
-        # (8 x bf16) vector loads stay aligned for every member
+        # (8 x bf16, or 4 x fp32) vector loads stay aligned for every member
         self.row_stride = (self.n + 7) // 8 * 8
-        self.weights = torch.empty((self.M, self.row_stride), dtype=torch.bfloat16, device=d)
+        self.weights = torch.empty(
+            (self.M, self.row_stride),
+            dtype=torch.float32 if self.fp32 else torch.bfloat16, device=d)
         self.offsets = torch.zeros(self.M, dtype=torch.int64, device=d)
         self.signs = torch.cat([torch.ones(self.pairs), -torch.ones(self.pairs),
                                 torch.zeros(1)]).to(d)
@@ -305,6 +336,19 @@ class GpuEngine:
         perturbation distribution)."""
         return float(self.policy.std) if self.eps_fp8 else 0.0
 
+    @property
+    def numerics(self) -> dict:
+        """Which numerics this engine evaluates the population on: weight
+        precision, sigma*eps stream encoding ("none": materialized member
+        rows), rollout path and launch mode — for logs and tools."""
+        if self.pair_rollout:
+            path, enc = "pair", "e4m3" if self.eps_fp8 else "bf16"
+        else:
+            path = "split" if self.split_dyn else "fused" if self.fused else "generic"
+            enc = "none"
+        return {"weights": self.weights_dtype, "eps_encoding": enc, "path": path,
+                "rollout_mode": self.rollout_mode}
+
     # ------------------------------------------------------------------ ops
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream if \
@@ -334,13 +378,17 @@ class GpuEngine:
                 self._one_signs.data_ptr(), self.pairs, self.n, self.row_stride,
                 std, self._stream()), "es_pheno_bf16")
             return
-        ops.check(ops.hip().es_pheno_bf16(
+        fn, name = (ops.hip().es_pheno_f32, "es_pheno_f32") if self.fp32 else \
+            (ops.hip().es_pheno_bf16, "es_pheno_bf16")
+        ops.check(fn(
             self.weights.data_ptr(), self.theta.data_ptr(), self.nt.noise.data_ptr(),
             self.offsets.data_ptr(), self.signs.data_ptr(), self.M, self.n,
-            self.row_stride, std, self._stream()), "es_pheno_bf16")
+            self.row_stride, std, self._stream()), name)
 
     def _forward(self, obs: torch.Tensor, salt: int):
-        ops.check(ops.hip().es_mlp_fwd(
+        fn, name = (ops.hip().es_mlp_fwd_f32, "es_mlp_fwd_f32") if self.fp32 else \
+            (ops.hip().es_mlp_fwd, "es_mlp_fwd")
+        ops.check(fn(
             self.actions.data_ptr(), obs.data_ptr(), self.weights.data_ptr(),
             self.obmean.data_ptr(), self.obstd.data_ptr(),
             self.dims_arr.ctypes.data, len(self.dims_arr), self.seed_dev.data_ptr(),
@@ -349,7 +397,7 @@ class GpuEngine:
             self.act_mode,
             self.alow_dev.data_ptr() if self.alow_dev is not None else None,
             self.arange_dev.data_ptr() if self.arange_dev is not None else None,
-            self._stream()), "es_mlp_fwd")
+            self._stream()), name)
         return self.actions
 
     def _loco_step(self, t: int):
@@ -402,6 +450,9 @@ class GpuEngine:
             ops.check(ops.hip().es_loco_step_split(
                 *common, self.act_scratch.data_ptr(), self.dyn_group,
                 self._stream()), "es_loco_step_split")
+        elif self.fp32:
+            ops.check(ops.hip().es_loco_step_f32(*common, self._stream()),
+                      "es_loco_step_f32")
         else:
             ops.check(ops.hip().es_loco_step(*common, self._stream()), "es_loco_step")
 
@@ -415,7 +466,9 @@ class GpuEngine:
         blob serves the noiseless slots, whose weights row is wrow0)."""
         env = self.env
         goal_ptr = env.goal.data_ptr() if env.goal_conditioned else None
-        ops.check(ops.hip().es_loco_episode(
+        fn, name = (ops.hip().es_loco_episode_f32, "es_loco_episode_f32") \
+            if self.fp32 else (ops.hip().es_loco_episode, "es_loco_episode")
+        ops.check(fn(
             self.weights.data_ptr() if weights_ptr is None else weights_ptr,
             self.obmean.data_ptr(), self.obstd.data_ptr(),
             self.dims_arr.ctypes.data, len(self.dims_arr), self.seed_dev.data_ptr(),
@@ -433,7 +486,7 @@ class GpuEngine:
             self.bins, self.eps, self.act_mode,
             float(env.leak), float(env.ctrl_cost), float(env.alive_bonus),
             float(env.fall_threshold), float(env.dt), int(block_threads),
-            self._stream()), "es_loco_episode")
+            self._stream()), name)
 
     def _loco_pair_episode(self, n_steps: Optional[int] = None, salt_base: int = 0):
         """n_steps consecutive env steps for every (pair, episode) block in
@@ -621,14 +674,17 @@ class GpuEngine:
                 self._zero_sign.data_ptr(), 1, self.n, self.row_stride, 0.0,
                 self._stream()), "es_pheno_bf16")
         elif self.device.type == "cuda":
-            # bf16(theta) into the noiseless slot's weights row (sign 0)
-            ops.check(ops.hip().es_pheno_bf16(
+            # theta (bf16-rounded, or as is in fp32 mode) into the noiseless
+            # slot's weights row (sign 0)
+            fn, name = (ops.hip().es_pheno_f32, "es_pheno_f32") if self.fp32 else \
+                (ops.hip().es_pheno_bf16, "es_pheno_bf16")
+            ops.check(fn(
                 self.weights[self.M - 1:].data_ptr(), self.theta.data_ptr(),
                 self.nt.noise.data_ptr(), self._zero_off.data_ptr(),
                 self._zero_sign.data_ptr(), 1, self.n, self.row_stride, 0.0,
-                self._stream()), "es_pheno_bf16")
+                self._stream()), name)
         else:
-            self.weights[self.M - 1, :self.n] = self.theta.bfloat16()
+            self.weights[self.M - 1, :self.n] = self.theta.to(self.weights.dtype)
         self._reset_rollout_state()
         self.obs_buf.copy_(self.env.reset(self._gen_seed()))
         self.acstd_dev.fill_(0.0)  # reference noiseless eval: use_ac_noise False

@@ -199,7 +199,14 @@ def _bind_hip(lib):
                                     p, p, p, p, p, p,
                                     i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                     i32, i32, f32, f32, f32, f32, f32, i32, p]
-    for fn in ["es_noise_fill", "es_pheno_bf16", "es_pheno_fp8", "es_mlp_fwd",
+    # fp32-weights entry points: the argument lists of their bf16 counterparts
+    lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
+    lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes
+    lib.es_loco_step_f32.argtypes = lib.es_loco_step.argtypes
+    lib.es_loco_episode_f32.argtypes = lib.es_loco_episode.argtypes
+    for fn in ["es_pheno_f32", "es_mlp_fwd_f32", "es_loco_step_f32",
+               "es_loco_episode_f32",
+               "es_noise_fill", "es_pheno_bf16", "es_pheno_fp8", "es_mlp_fwd",
                "es_grad_gather", "es_adam_step", "es_sgd_step", "es_loco_step",
                "es_loco_step_split", "es_loco_pair_step", "es_loco_pair_step_fp8",
                "es_loco_pair_episode", "es_loco_episode"]:

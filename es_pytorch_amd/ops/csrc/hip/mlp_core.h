@@ -6,7 +6,8 @@
 // W^T[i][8*oi..+7] as one 16-B uint4 (1 KiB per wave-instruction) and FMAs
 // into 8 independent accumulator chains; partials reduce across i-partitions
 // through LDS; bias + tanh in the epilogue. Non-8-aligned layers (the tiny
-// action head) take a scalar fallback.
+// action head) take a scalar fallback. mlp_layers_f32 is the fp32-weights
+// counterpart (quads of float instead of octets of bf16).
 #pragma once
 #include "common.h"
 
@@ -255,6 +256,145 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
           }
           for (; i < I; ++i) acc = fmaf(bf2f(Wt[(int64_t)i * O + o]), x[i], acc);
 #endif
+          y[o] = do_act ? tanhf(acc) : acc;
+        }
+      }
+    }
+    __syncthreads();
+    float* t = x;
+    x = y;
+    y = t;
+  }
+  return x;
+}
+
+// ---- fp32-weights forward ---------------------------------------------------
+// weights_dtype = "fp32": the member rows hold float32(theta + s*eps) and the
+// forward accumulates them with fp32 fmaf, so the only difference from the
+// reference's fp32 forward is summation order. Same per-layer scheme as
+// mlp_layers (partition the i-walk, reduce partials through LDS, bias + tanh
+// in the epilogue).
+//
+// Tiling: QUADS. A thread owns 4 outputs and issues ONE 16-B load per row:
+// the same 16 B per lane / 1 KiB per wave-instruction as the bf16 octet, and
+// the same register footprint at pipeline depth 4 (8 x 16 B in flight + 4
+// accumulators instead of 8). Octets with two loads per row would keep the
+// (PART, OCT, 8) partial layout but double the live load registers (64
+// VGPRs of weights at depth 4) for no extra bytes per wave-instruction. With
+// quads QT = O/4 tiles and PART = nthreads / QT i-partitions; the partial
+// layout (ip, o) is PART x O floats. A layer wider than 4 * nthreads
+// (QT > nthreads, e.g. O = 2048 at 256 threads) runs PART = 1 and each
+// thread sweeps tiles tid, tid + nthreads, ...; the partial slab is then O
+// <= ES_MAXDIM floats, which is exactly the 256*8 floats every caller carves.
+//
+// A layer is quad-tiled when O % 4 == 0 and its weight block AND the member
+// row are 16-B aligned (woff % 4 == 0, row_stride % 4 == 0); everything else
+// takes the scalar walks, so no vector load can be misaligned. Every load is
+// guarded by its own row index < I: the blob has no guard row and needs none.
+static inline void mlp_shape_vec_f32(MlpShape* sh, int64_t row_stride) {
+  for (int l = 0; l < sh->n_layers; ++l)
+    sh->vec_ok[l] = (sh->dims[l + 1] % 4 == 0) && (sh->woff[l] % 4 == 0) &&
+                    (row_stride % 4 == 0);
+}
+
+__device__ __forceinline__ void f4_fma(uint4 w, const float xi, float* acc) {
+  acc[0] = fmaf(__uint_as_float(w.x), xi, acc[0]);
+  acc[1] = fmaf(__uint_as_float(w.y), xi, acc[1]);
+  acc[2] = fmaf(__uint_as_float(w.z), xi, acc[2]);
+  acc[3] = fmaf(__uint_as_float(w.w), xi, acc[3]);
+}
+
+__device__ __forceinline__ float* mlp_layers_f32(const float* __restrict__ wb,
+                                                 const MlpShape& sh,
+                                                 float* bufA, float* bufB, float* partial,
+                                                 int tid, int nthreads, int act_final) {
+  float* x = bufA;
+  float* y = bufB;
+  for (int l = 0; l < sh.n_layers; ++l) {
+    const int I = sh.dims[l], O = sh.dims[l + 1];
+    const float* Wt = wb + sh.woff[l];
+    const float* Bs = wb + sh.boff[l];
+    const bool do_act = (l < sh.n_layers - 1) || act_final;
+
+    if (sh.vec_ok[l]) {
+      const int QT = O >> 2;
+      const bool wide = QT > nthreads;  // block-uniform
+      const int PART = wide ? 1 : nthreads / QT;
+      const int ip = wide ? 0 : tid / QT;
+      if (ip < PART) {
+        for (int oi = wide ? tid : tid % QT; oi < QT; oi += nthreads) {
+          float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+          const float* wcol = Wt + (oi << 2);
+          // nt 16-B loads, depth-4 register double-buffer: see mlp_layers.
+          // The quad is carried as four u32 lanes exactly like the bf16
+          // octet: with a float4-typed carried value the optimizer folds
+          // the loop-carried phi(prologue load, next load) back into ONE
+          // load at the loop head, i.e. load 4 -> wait -> FMA per trip with
+          // nothing in flight across the back-edge (seen in the ISA).
+          typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+          auto ld = [&](int i) {
+            u32x4v v = __builtin_nontemporal_load(
+                reinterpret_cast<const u32x4v*>(wcol + (int64_t)i * O));
+            uint4 w;
+            w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
+            return w;
+          };
+          int i = ip;
+          const int step4 = PART * 4;
+          if (i + 3 * PART < I) {
+            uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART),
+                  c3 = ld(i + 3 * PART);
+            for (; i + 7 * PART < I; i += step4) {
+              const uint4 n0 = ld(i + 4 * PART), n1 = ld(i + 5 * PART),
+                          n2 = ld(i + 6 * PART), n3 = ld(i + 7 * PART);
+              f4_fma(c0, x[i], acc);
+              f4_fma(c1, x[i + PART], acc);
+              f4_fma(c2, x[i + 2 * PART], acc);
+              f4_fma(c3, x[i + 3 * PART], acc);
+              c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+            }
+            f4_fma(c0, x[i], acc);
+            f4_fma(c1, x[i + PART], acc);
+            f4_fma(c2, x[i + 2 * PART], acc);
+            f4_fma(c3, x[i + 3 * PART], acc);
+            i += step4;
+          }
+          for (; i < I; i += PART) f4_fma(ld(i), x[i], acc);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) partial[ip * O + (oi << 2) + q] = acc[q];
+        }  // one trip unless wide: oi + nthreads >= QT
+      }
+      __syncthreads();
+      for (int o = tid; o < O; o += nthreads) {
+        float s = Bs[o];
+        for (int p = 0; p < PART; ++p) s += partial[p * O + o];
+        y[o] = do_act ? tanhf(s) : s;
+      }
+    } else {
+      // scalar layers (the action head, odd widths, misaligned blocks): the
+      // batched row walk of mlp_layers with W = float
+      const int PART = nthreads / O;
+      if (PART > 1) {
+        const int oi = tid % O, ip = tid / O;
+        float acc = 0.0f;
+        if (ip < PART) {
+          es_walk_batched<float>(
+              ip, PART, I, [&](int r) { return Wt[(int64_t)r * O + oi]; },
+              [&](float w, int r) { acc = fmaf(w, x[r], acc); });
+          partial[ip * O + oi] = acc;
+        }
+        __syncthreads();
+        for (int o = tid; o < O; o += nthreads) {
+          float s = Bs[o];
+          for (int p = 0; p < PART; ++p) s += partial[p * O + o];
+          y[o] = do_act ? tanhf(s) : s;
+        }
+      } else {
+        for (int o = tid; o < O; o += nthreads) {
+          float acc = Bs[o];
+          es_walk_batched<float>(
+              0, 1, I, [&](int r) { return Wt[(int64_t)r * O + o]; },
+              [&](float w, int r) { acc = fmaf(w, x[r], acc); });
           y[o] = do_act ? tanhf(acc) : acc;
         }
       }

@@ -47,6 +47,55 @@ __global__ void pheno_bf16_kernel(uint16_t* __restrict__ out, const float* __res
   for (; t < n_params; ++t) ob[t] = f2bf(theta[t] + s * noise[t]);
 }
 
+// ---- fp32 member rows (weights_dtype = "fp32") ------------------------------
+//   out[b][t] = fmaf(sign[b] * std, table[offset[b] + t], theta[t])
+// One rounding per element, written as an explicit fmaf so the result does
+// not depend on the compiler's contraction setting; a sign-0 row is theta
+// bit for bit. Thread owns 4 consecutive elements: theta reads as one float4
+// and the row (16-B aligned: row_stride % 4 == 0) writes as ONE 16-B store;
+// the noise loads stay scalar (arbitrary 4-B alignment), as above. Elements
+// [n_params, row_stride) are not written.
+__global__ void pheno_f32_kernel(float* __restrict__ out, const float* __restrict__ theta,
+                                 const float* __restrict__ table,
+                                 const int64_t* __restrict__ offsets,
+                                 const float* __restrict__ signs, int64_t n_params,
+                                 int64_t row_stride, float std) {
+  const int64_t b = blockIdx.y;
+  const float s = signs[b] * std;
+  const float* noise = table + offsets[b];
+  float* ob = out + b * row_stride;
+  const int64_t stride4 = (int64_t)gridDim.x * blockDim.x * 4;
+  int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  for (; t + 3 < n_params; t += stride4) {
+    const float4 th = *reinterpret_cast<const float4*>(theta + t);
+    float nz[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) nz[k] = noise[t + k];
+    float4 v;
+    v.x = fmaf(s, nz[0], th.x);
+    v.y = fmaf(s, nz[1], th.y);
+    v.z = fmaf(s, nz[2], th.z);
+    v.w = fmaf(s, nz[3], th.w);
+    *reinterpret_cast<float4*>(ob + t) = v;
+  }
+  for (; t < n_params; ++t) ob[t] = fmaf(s, noise[t], theta[t]);
+}
+
+// Same argument list as es_pheno_bf16; out is float*, row_stride in elements.
+extern "C" int es_pheno_f32(void* out, const void* theta, const void* table,
+                            const void* offsets, const void* signs, int64_t n_pop,
+                            int64_t n_params, int64_t row_stride, float std, void* stream) {
+  if (row_stride < n_params || row_stride % 4 != 0) return -102;
+  int threads = 256;
+  int bx = (int)std::min<int64_t>((n_params + threads * 4 - 1) / (threads * 4), 1024);
+  dim3 grid(bx, (unsigned)n_pop);
+  pheno_f32_kernel<<<grid, dim3(threads), 0, (hipStream_t)stream>>>(
+      (float*)out, (const float*)theta, (const float*)table, (const int64_t*)offsets,
+      (const float*)signs, n_params, row_stride, std);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---- fp8 sigma*eps blob -----------------------------------------------------
 // The antithetic-pair rollout's dominant cost is streaming the per-pair
 // sigma*eps rows from HBM. fp8 (OCP e4m3fn) halves those bytes AND halves

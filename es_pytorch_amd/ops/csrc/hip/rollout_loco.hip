@@ -141,6 +141,10 @@ __device__ __forceinline__ void loco_decode_action(
   }
 }
 
+// WT = uint16_t: P.weights is the bf16 member blob (mlp_layers); WT = float:
+// the same pointer holds float32 rows (weights_dtype = "fp32",
+// mlp_layers_f32). row_stride counts elements of WT either way.
+template <typename WT = uint16_t>
 __device__ __forceinline__ void loco_fwd_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P, int b, uint64_t salt,
     float* bufA, float* bufB, float* partial, float* raws, float* abuf) {
@@ -148,8 +152,13 @@ __device__ __forceinline__ void loco_fwd_body(
   const int nth = blockDim.x;
   loco_build_obs(la, P, b, bufA, raws, tid, nth);
   __syncthreads();
-  const uint16_t* wb = P.weights + (int64_t)(b / la.eps - la.wrow0) * la.row_stride;
-  const float* aout = mlp_layers(wb, sh, bufA, bufB, partial, tid, nth, 1);
+  const WT* wb = reinterpret_cast<const WT*>(P.weights) +
+                 (int64_t)(b / la.eps - la.wrow0) * la.row_stride;
+  const float* aout;
+  if constexpr (sizeof(WT) == 4)
+    aout = mlp_layers_f32(wb, sh, bufA, bufB, partial, tid, nth, 1);
+  else
+    aout = mlp_layers(wb, sh, bufA, bufB, partial, tid, nth, 1);
   loco_decode_action(sh, la, P, b, salt, aout, abuf, tid);
   __syncthreads();
 }
@@ -471,10 +480,11 @@ __device__ __forceinline__ void loco_dyn_finish_pair(
 #endif
 }
 
+template <typename WT = uint16_t>
 __device__ __forceinline__ void loco_step_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P, int b, uint64_t salt,
     float* bufA, float* bufB, float* partial, float* raws, float* abuf, float* sc) {
-  loco_fwd_body(sh, la, P, b, salt, bufA, bufB, partial, raws, abuf);
+  loco_fwd_body<WT>(sh, la, P, b, salt, bufA, bufB, partial, raws, abuf);
   if (la.S % 8 == 0)
     loco_dyn_partials(P.Am, la.S, raws, partial, threadIdx.x, blockDim.x);
   loco_dyn_finish(la, P, b, raws, abuf, partial, threadIdx.x, blockDim.x);
@@ -524,6 +534,44 @@ loco_episode512_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
   for (int t = 1; t <= n_steps; ++t)
     loco_step_body(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial, raws,
                    abuf, sc);
+}
+
+// ---- fp32-weights variants (weights_dtype = "fp32") ------------------------
+// The step and episode kernels above with the fp32 forward (mlp_layers_f32);
+// obs build, action decode, dynamics, epilogue and bookkeeping are the same
+// device functions, and A stays the env's bf16-valued matrix. Same LDS
+// carve: the quad partials need PART * O <= nthreads * 4 floats, or O <=
+// ES_MAXDIM = 256 * 8 floats when a layer is wider than 4 * nthreads.
+__global__ void __launch_bounds__(256)
+loco_step_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, uint64_t salt) {
+  ES_LOCO_CARVE();
+  loco_step_body<float>(sh, la, P, blockIdx.x, salt, bufA, bufB, partial, raws, abuf, sc);
+}
+
+__global__ void __launch_bounds__(256)
+loco_episode_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
+                        int n_steps, int salt_base) {
+  ES_LOCO_CARVE();
+  const int b = member_base + blockIdx.x;
+  for (int t = 1; t <= n_steps; ++t)
+    loco_step_body<float>(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial,
+                          raws, abuf, sc);
+}
+
+__global__ void __launch_bounds__(512)
+loco_episode512_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
+                           int n_steps, int salt_base) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* bufA = reinterpret_cast<float*>(smem);
+  float* bufB = bufA + sh.maxdim;
+  float* partial = bufB + sh.maxdim;
+  float* raws = partial + 512 * 8;
+  float* abuf = raws + ((la.S + 3) & ~3);
+  float* sc = abuf + 64;
+  const int b = member_base + blockIdx.x;
+  for (int t = 1; t <= n_steps; ++t)
+    loco_step_body<float>(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial,
+                          raws, abuf, sc);
 }
 
 // ---- split-dynamics path ---------------------------------------------------
@@ -1085,6 +1133,73 @@ extern "C" int es_loco_episode(const void* weights, const void* obmean, const vo
     loco_episode_kernel<<<dim3((unsigned)n_members), dim3(256), lds,
                           (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
                                                  salt_base);
+  }
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// fp32-weights step / episode: the argument lists of es_loco_step and
+// es_loco_episode; `weights` is float32 (rows, row_stride), row_stride in
+// elements.
+extern "C" int es_loco_step_f32(
+    const void* weights, const void* obmean, const void* obstd,
+    const int32_t* dims_host, int32_t ndims, const void* seed_dev, uint64_t salt,
+    float ob_clip, const void* ac_std_dev, int64_t row_stride, void* s_glob, void* pos,
+    const void* goal, const void* Am, const void* Bm, const void* b0, const void* wv,
+    const void* wa, const void* wy, const void* wh, void* alive, void* rew_total,
+    void* member_steps, void* behv, void* mo_sum, void* mo_sumsq, int32_t n_pop,
+    int32_t sdim, int32_t adim, int32_t goal_flag, int32_t terminate,
+    int32_t noiseless_from, int32_t bins, int32_t eps, int32_t act_mode, float leak,
+    float ctrl, float alive_bonus, float fall_thr, float dt, void* stream) {
+  MlpShape sh;
+  LocoArgs la;
+  unsigned lds;
+  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
+                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
+                        ctrl, alive_bonus, fall_thr, dt, &lds);
+  if (rc) return rc;
+  mlp_shape_vec_f32(&sh, row_stride);
+  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
+                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
+                         mo_sum, mo_sumsq);
+  loco_step_f32_kernel<<<dim3((unsigned)n_pop), dim3(256), lds, (hipStream_t)stream>>>(
+      sh, la, P, salt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int es_loco_episode_f32(
+    const void* weights, const void* obmean, const void* obstd,
+    const int32_t* dims_host, int32_t ndims, const void* seed_dev, int32_t n_steps,
+    float ob_clip, const void* ac_std_dev, int64_t row_stride, void* s_glob, void* pos,
+    const void* goal, const void* Am, const void* Bm, const void* b0, const void* wv,
+    const void* wa, const void* wy, const void* wh, void* alive, void* rew_total,
+    void* member_steps, void* behv, void* mo_sum, void* mo_sumsq, int32_t member_base,
+    int32_t n_members, int32_t salt_base, int32_t wrow0, int32_t sdim, int32_t adim,
+    int32_t goal_flag, int32_t terminate, int32_t noiseless_from, int32_t bins,
+    int32_t eps, int32_t act_mode, float leak, float ctrl, float alive_bonus,
+    float fall_thr, float dt, int32_t block_threads, void* stream) {
+  MlpShape sh;
+  LocoArgs la;
+  unsigned lds;
+  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
+                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
+                        ctrl, alive_bonus, fall_thr, dt, &lds);
+  if (rc) return rc;
+  mlp_shape_vec_f32(&sh, row_stride);
+  la.wrow0 = wrow0;
+  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
+                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
+                         mo_sum, mo_sumsq);
+  if (block_threads == 512) {
+    const unsigned lds512 = lds + 256 * 8 * 4;  // partial[] grows with nth
+    loco_episode512_f32_kernel<<<dim3((unsigned)n_members), dim3(512), lds512,
+                                 (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
+                                                        salt_base);
+  } else {
+    loco_episode_f32_kernel<<<dim3((unsigned)n_members), dim3(256), lds,
+                              (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
+                                                     salt_base);
   }
   ES_CHECK_LAUNCH();
   return 0;

@@ -32,6 +32,8 @@ def main():
     p.add_argument("--dyn-group", type=int, default=5,
                    help="members per dynamics block in split mode")
     p.add_argument("--fp8", action="store_true", help="fp8 sigma*eps stream")
+    p.add_argument("--fp32", action="store_true",
+                   help="fp32 member rows + fp32-weight forward (weights_dtype=fp32)")
     args = p.parse_args()
 
     from es_pytorch_amd.config import AttrDict
@@ -65,7 +67,8 @@ def main():
     eng = GpuEngine(cfg, comm, policy, nt, env, rs, use_graph=args.graph,
                     rollout_mode="episode" if args.episode else "step",
                     split_dyn=args.split or None, pair_rollout=args.pair or None,
-                    eps_fp8=args.fp8 or None)
+                    eps_fp8=args.fp8 or None,
+                    weights_dtype="fp32" if args.fp32 else None)
     ranker = CenteredRanker()
     eng.step(ranker)  # warmup
 
@@ -75,7 +78,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"gen: {dt*1e3:.2f} ms  per-step: {dt/args.steps*1e6:.1f} us  "
-          f"timings={eng.timings}")
+          f"numerics={eng.numerics} timings={eng.timings}")
 
 
 if __name__ == "__main__":
