@@ -31,6 +31,82 @@
 #endif
 #define ES_HEAD_BT 8
 
+// ES_STREAM_PIPE: the steady loops of the fp8 pair forward (vec branch of
+// mlp_layers_pair_fp8) and of the pair A stream (loco_dyn_partials_pair) keep
+// their loaded rows in named register SETS that change role over an unrolled
+// loop of whole turns (forward: 2 sets of 2 row pairs, period 2; A stream: 3
+// sets of 4 rows, period 3): each sub-trip issues the loads of the free set,
+// then consumes the oldest, so there is nothing to rotate by copy and a load
+// is first waited for one (forward) or two (A stream) sub-trips after it
+// issues. (The old "next = load; consume cur; cur = next" loops compiled to
+// a copy of the just-loaded registers, hence a wait for the trip's own loads
+// at the bottom of every trip.) What it took to make the compiler keep that
+// shape: the FMAs are written as two-lane fmas (bf8_fma_pk), because the
+// vectorizer, left to find the packed form, re-orders the block and sinks a
+// sub-trip's FMAs below the next refill of their set; a sched_barrier
+// between sub-trips; one loop exit (a multi-exit loop is restructured with
+// copies on the back edge). The turn count is the block-uniform minimum; the
+// rows a lane still owns behind the ring load ahead of the drain's FMAs, so
+// no row takes a serialized tail load once the ring is in use. Per-thread
+// FMA order (ascending row into the same accumulators) and the t+e / t-e
+// roundings are unchanged -> bitwise-same results. 0 restores the old loops.
+#ifndef ES_STREAM_PIPE
+#define ES_STREAM_PIPE 1
+#endif
+// ES_STREAM_SADDR: addressing of the ring loads. 0 (default): base +
+// (int64)row * stride per lane, which the compiler strength-reduces inside
+// the ring loops to one 64-bit per-lane pointer per stream and uniform
+// steps (no v_mad_i64_i32 left in the loops). 1: a wave-uniform 64-bit base
+// in scalar registers plus one 32-bit per-lane byte offset, i.e. the
+// scalar-base form of global_load with one 32-bit vector add per load. The
+// scalar-base form measured 2% SLOWER on the flagship (6 alternated runs
+// each), so it is the knob and not the default.
+#ifndef ES_STREAM_SADDR
+#define ES_STREAM_SADDR 0
+#endif
+
+typedef uint32_t es_u32x4 __attribute__((ext_vector_type(4)));
+
+// Row-strided 16-B stream: thread reads bytes [lane, lane+16) of rows
+// row0 + k*rstep (k = 0, 1, ...) of a matrix with `rbytes` bytes per row.
+// lane < 2^32 is the caller's to guarantee (ES_MAXDIM^2 * 2 B = 8 MiB).
+struct EsRowStream {
+#if ES_STREAM_SADDR
+  const char* ub;  // uniform base
+  uint32_t lane;   // per-lane byte offset of the cursor row
+  uint32_t sb;     // uniform bytes per k
+  __device__ __forceinline__ EsRowStream(const void* base, int row0, int rstep,
+                                         int rbytes, int lane_bytes)
+      : ub(reinterpret_cast<const char*>(base)),
+        lane((uint32_t)(row0 * rbytes + lane_bytes)),
+        sb((uint32_t)(rstep * rbytes)) {}
+  // the 32-bit sum keeps the scalar-base + 32-bit-lane-offset load form
+  // (a 64-bit sum is re-associated into a per-lane 64-bit pointer)
+  __device__ __forceinline__ const char* at(int k) const {
+    return ub + (size_t)(uint32_t)(lane + (uint32_t)k * sb);
+  }
+  __device__ __forceinline__ void advance(int k) { lane += (uint32_t)k * sb; }
+#else
+  const char* lb;  // per-lane column base
+  int row, rstep;
+  int64_t rbytes;
+  __device__ __forceinline__ EsRowStream(const void* base, int row0, int rstep_,
+                                         int rbytes_, int lane_bytes)
+      : lb(reinterpret_cast<const char*>(base) + lane_bytes),
+        row(row0), rstep(rstep_), rbytes(rbytes_) {}
+  __device__ __forceinline__ const char* at(int k) const {
+    return lb + (int64_t)(row + k * rstep) * rbytes;
+  }
+  __device__ __forceinline__ void advance(int k) { row += k * rstep; }
+#endif
+  __device__ __forceinline__ es_u32x4 ld(int k) const {
+    return *reinterpret_cast<const es_u32x4*>(at(k));
+  }
+  __device__ __forceinline__ es_u32x4 ld_nt(int k) const {
+    return __builtin_nontemporal_load(reinterpret_cast<const es_u32x4*>(at(k)));
+  }
+};
+
 // Guarded drain of es_walk_batched: R rows every thread owns, then the one
 // row only some threads own. All R + 1 loads issue ahead of the first FMA;
 // the conditional row's load is clamped to row 0 where the thread has none.
@@ -123,6 +199,26 @@ __device__ __forceinline__ void bf8_fma(uint4 w, const float xi, float* acc) {
   for (int q = 0; q < 4; ++q) {
     acc[2 * q] = fmaf(bf2f((uint16_t)(ws[q] & 0xFFFFu)), xi, acc[2 * q]);
     acc[2 * q + 1] = fmaf(bf2f((uint16_t)(ws[q] >> 16)), xi, acc[2 * q + 1]);
+  }
+}
+
+__device__ __forceinline__ uint4 es_as_uint4(es_u32x4 v) {
+  uint4 w;
+  w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
+  return w;
+}
+
+// bf8_fma on accumulator PAIRS: acc2[q] = (acc[2q], acc[2q+1]). The same
+// eight fmaf, written as four two-lane fmas so the packed form does not hang
+// on the vectorizer finding it (which also re-orders the block to do so).
+__device__ __forceinline__ void bf8_fma_pk(es_u32x4 w, float xi, es_f32x2* acc2) {
+  const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+  const es_f32x2 x2 = {xi, xi};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const es_f32x2 w2 = {__builtin_bit_cast(float, ws[q] << 16),
+                         __builtin_bit_cast(float, ws[q] & 0xFFFF0000u)};
+    acc2[q] = __builtin_elementwise_fma(w2, x2, acc2[q]);
   }
 }
 
@@ -426,6 +522,28 @@ __device__ __forceinline__ void bf8e_fma_pair(uint4 t, const float* e8, float xp
   }
 }
 
+// bf8e_fma_pair on accumulator PAIRS (see bf8_fma_pk): theta octet (bf16)
+// +- the eps octet held as two fp8x4 words, FMA'd into both members. Lane
+// for lane the same t+e / t-e roundings and fmaf as bf8e_fma_pair after
+// fp8x4_decode(elo), fp8x4_decode(ehi).
+__device__ __forceinline__ void bf8e_fma_pair_pk(es_u32x4 t, uint32_t elo, uint32_t ehi,
+                                                 float xp, float xm, es_f32x2* ap,
+                                                 es_f32x2* am) {
+  const uint32_t ts[4] = {t.x, t.y, t.z, t.w};
+  const es_f32x2 e2[4] = {__builtin_amdgcn_cvt_pk_f32_fp8(elo, false),
+                          __builtin_amdgcn_cvt_pk_f32_fp8(elo, true),
+                          __builtin_amdgcn_cvt_pk_f32_fp8(ehi, false),
+                          __builtin_amdgcn_cvt_pk_f32_fp8(ehi, true)};
+  const es_f32x2 xp2 = {xp, xp}, xm2 = {xm, xm};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const es_f32x2 t2 = {__builtin_bit_cast(float, ts[q] << 16),
+                         __builtin_bit_cast(float, ts[q] & 0xFFFF0000u)};
+    ap[q] = __builtin_elementwise_fma(t2 + e2[q], xp2, ap[q]);
+    am[q] = __builtin_elementwise_fma(t2 - e2[q], xm2, am[q]);
+  }
+}
+
 // mlp_layers_pair with an fp8 (OCP e4m3fn) sigma*eps blob: one nt 16-B load
 // covers one octet of TWO consecutive i-rows (pheno_fp8_kernel's row-pair
 // interleave), halving both the bytes and the load count of the HBM eps
@@ -495,7 +613,93 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         }
         int i2 = ip;
         const int step2 = PART * 2;
-#if ES_FP8_WIDE4
+#if ES_STREAM_PIPE
+        // Two 2-row-pair sets that swap role by name over a steady loop of
+        // whole turns (see ES_STREAM_PIPE): a sub-trip fills one set with
+        // the next two row pairs, then consumes the other. Every lane owns
+        // nmin or nmin + 1 row pairs; the turn count is block-uniform, and
+        // the 0..4 row pairs a lane has left behind the held set load ahead
+        // of the drain.
+        const int nmin = I2 / PART;
+        if (nmin >= 2) {
+          const int T = (nmin - 2) >> 2;
+          const int rem = (I2 - 1 - ip) / PART + 1 - 4 * T - 2;
+          // one stream step = one row pair: 2*O fp8 bytes, two bf16 rows
+          EsRowStream es(Et8 + (int64_t)ro * O, ip, PART, 2 * O, oi << 4);
+          EsRowStream ta(Tt + (int64_t)ro * O, ip, PART, 4 * O, oi << 4);
+          EsRowStream tb(Tt + (int64_t)(ro + 1) * O, ip, PART, 4 * O, oi << 4);
+          const float* xqp = xp + ro + 2 * ip;
+          const float* xqm = xm + ro + 2 * ip;
+          es_f32x2 a2p[4], a2m[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            a2p[q] = es_f32x2{accp[2 * q], accp[2 * q + 1]};
+            a2m[q] = es_f32x2{accm[2 * q], accm[2 * q + 1]};
+          }
+          struct Slot { es_u32x4 e, a, b; };
+          auto ldslot = [&](Slot& s, int k) {
+            s.e = es.ld_nt(k);
+            s.a = ta.ld(k);
+            s.b = tb.ld(k);
+          };
+          auto eatslot = [&](const Slot& s, int k) {
+            const float* qp = xqp + 2 * k * PART;
+            const float* qm = xqm + 2 * k * PART;
+            bf8e_fma_pair_pk(s.a, s.e.x, s.e.y, qp[0], qm[0], a2p, a2m);
+            bf8e_fma_pair_pk(s.b, s.e.z, s.e.w, qp[1], qm[1], a2p, a2m);
+          };
+          struct Set { Slot s[2]; };
+          auto fill = [&](Set& w) {
+            ldslot(w.s[0], 0);
+            ldslot(w.s[1], 1);
+            es.advance(2);
+            ta.advance(2);
+            tb.advance(2);
+          };
+          auto eat = [&](const Set& w) {
+            eatslot(w.s[0], 0);
+            eatslot(w.s[1], 1);
+            xqp += 4 * PART;
+            xqm += 4 * PART;
+          };
+          Set c, n;
+          fill(c);
+          // the fences keep a sub-trip's work out of the next one, where
+          // the set it reads is refilled
+          for (int t = T; t > 0; --t) {
+            fill(n); eat(c);
+            __builtin_amdgcn_sched_barrier(0);
+            fill(c); eat(n);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          // drain: the 0..4 row pairs left load into fresh names, each two
+          // slots ahead of its FMAs, so no more is live than in the loop.
+          // (Zeroed first: an undefined "not loaded" value is hoisted out
+          // of the layer loop as 48 live registers.)
+          Slot f[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) f[k].e = f[k].a = f[k].b = es_u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+          for (int k = 0; k < 2; ++k)
+            if (k < rem) ldslot(f[k], k);
+          __builtin_amdgcn_sched_barrier(0);
+          eat(c);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (k + 2 < 4 && k + 2 < rem) ldslot(f[k + 2], k + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            if (k < rem) eatslot(f[k], k);
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            accp[2 * q] = a2p[q].x; accp[2 * q + 1] = a2p[q].y;
+            accm[2 * q] = a2m[q].x; accm[2 * q + 1] = a2m[q].y;
+          }
+          i2 = I2;  // every owned row pair is consumed
+        }
+        (void)step2;
+#elif ES_FP8_WIDE4
         // 4-wide (8 rows) pipeline: doubles the issue batch and lookahead
         const int step4w = PART * 4;
         if (i2 + 3 * PART < I2) {

@@ -694,6 +694,10 @@ static int loco_launch_dyn(const LocoArgs& la, const LocoPtrs& P, const float* a
 // Effective weights are bf16(theta) +- bf16(sigma*eps) (two roundings); with
 // sigma = 0 the trajectories are BITWISE-identical to es_loco_step.
 
+// PIPE = false keeps the ES_DYN_DEPTH8 loop whatever ES_STREAM_PIPE says: the
+// whole-episode kernel runs under a 128-VGPR bound with spills, and the set
+// ring adds to them.
+template <bool PIPE = true>
 __device__ __forceinline__ void loco_dyn_partials_pair(
     const uint16_t* Am, int S, const float* rawsP, const float* rawsM,
     float* partP, float* partM, int tid, int nth) {
@@ -714,6 +718,78 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
     };
     int i = ip;
     const int step4 = PART * 4;
+    constexpr bool kPipe = PIPE && ES_STREAM_PIPE;
+    if constexpr (kPipe) {
+    // Three 4-row sets that change role by name over a steady loop of
+    // whole turns (see ES_STREAM_PIPE, mlp_core.h): each sub-trip fills the
+    // free set 8 rows ahead, then consumes the oldest. Every lane owns nmin
+    // or nmin + 1 rows; the turn count is block-uniform, and the 0..12 rows
+    // a lane has left behind the two held sets load ahead of the drain.
+    const int nmin = S / PART;
+    if (nmin >= 8) {
+      const int T = (nmin - 8) / 12;
+      const int rem = (S - 1 - ip) / PART + 1 - 12 * T - 8;
+      EsRowStream as(Am, ip, PART, 2 * S, oi << 4);
+      const float* xP = rawsP + ip;
+      const float* xM = rawsM + ip;
+      es_f32x2 a2p[4], a2m[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a2p[q] = a2m[q] = es_f32x2{0.0f, 0.0f};
+      struct Set { es_u32x4 v[4]; };
+      auto fill = [&](Set& s) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s.v[k] = as.ld(k);
+        as.advance(4);
+      };
+      auto eat = [&](const Set& s) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          bf8_fma_pk(s.v[k], xP[k * PART], a2p);
+          bf8_fma_pk(s.v[k], xM[k * PART], a2m);
+        }
+        xP += 4 * PART;
+        xM += 4 * PART;
+      };
+      Set c, d, n;
+      fill(c);
+      fill(d);
+      // the fences keep a sub-trip's work out of the next one, where the
+      // set it reads is refilled
+      for (int t = T; t > 0; --t) {
+        fill(n); eat(c);
+        __builtin_amdgcn_sched_barrier(0);
+        fill(c); eat(d);
+        __builtin_amdgcn_sched_barrier(0);
+        fill(d); eat(n);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // drain: the rows left load into fresh names (merging with a set's
+      // stale rows would copy them), then c, d and they are consumed
+      es_u32x4 f[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k)
+        if (k < rem) f[k] = as.ld(k);
+      __builtin_amdgcn_sched_barrier(0);
+      eat(c);
+      __builtin_amdgcn_sched_barrier(0);
+      eat(d);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        if (k < rem) {
+          bf8_fma_pk(f[k], xP[k * PART], a2p);
+          bf8_fma_pk(f[k], xM[k * PART], a2m);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        accp[2 * q] = a2p[q].x; accp[2 * q + 1] = a2p[q].y;
+        accm[2 * q] = a2m[q].x; accm[2 * q + 1] = a2m[q].y;
+      }
+      i = S;  // every owned row is consumed
+    }
+    }
+    if constexpr (!kPipe) {
 #if ES_DYN_DEPTH8
     if (i + 7 * PART < S) {
       uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
@@ -759,6 +835,7 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
       i += step4;
     }
 #endif
+    }
     for (; i < S; i += PART) fma2(ld(i), i);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -780,7 +857,7 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
 #endif
 
 // EB = uint16_t (bf16 eps rows) or uint8_t (fp8 row-pair-interleaved rows)
-template <typename EB>
+template <typename EB, bool PIPE = true>
 __device__ __forceinline__ void loco_pair_step_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P,
     const uint16_t* tb, const EB* eb, int bp, int bm, uint64_t salt,
@@ -792,7 +869,7 @@ __device__ __forceinline__ void loco_pair_step_body(
   __syncthreads();
   const bool early = ES_DYN_EARLY && partA != nullptr && la.S % 8 == 0;
   if (early)
-    loco_dyn_partials_pair(P.Am, la.S, rawsP, rawsM, partA, partA + 2048,
+    loco_dyn_partials_pair<PIPE>(P.Am, la.S, rawsP, rawsM, partA, partA + 2048,
                            tid, nth);
   float *ap, *am;
   if constexpr (sizeof(EB) == 1)
@@ -806,7 +883,7 @@ __device__ __forceinline__ void loco_pair_step_body(
   __syncthreads();
   float* pd = early ? partA : partial;
   if (!early && la.S % 8 == 0)
-    loco_dyn_partials_pair(P.Am, la.S, rawsP, rawsM, partial, partial + 2048,
+    loco_dyn_partials_pair<PIPE>(P.Am, la.S, rawsP, rawsM, partial, partial + 2048,
                            tid, nth);
   loco_dyn_finish_pair(la, P, bp, bm, rawsP, rawsM, abufP, abufM, pd, pd + 2048, tid,
                        nth);
@@ -872,7 +949,7 @@ loco_pair_episode_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* t
   ES_LOCO_PAIR_CARVE();
 #pragma clang loop unroll(disable)
   for (int t = 1; t <= n_steps; ++t)
-    loco_pair_step_body(sh, la, P, tb, ebp, bp, bm, (uint64_t)(salt_base + t),
+    loco_pair_step_body<uint16_t, false>(sh, la, P, tb, ebp, bp, bm, (uint64_t)(salt_base + t),
                         bufAp, bufAm, bufBp, bufBm, partial, rawsP, rawsM, abufP,
                         abufM, partA);
 }
