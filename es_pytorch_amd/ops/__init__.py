@@ -23,8 +23,8 @@ from typing import Optional
 
 _DIR = os.path.dirname(os.path.abspath(__file__))
 _CPU_SO = os.path.join(_DIR, "_cpu_ops.so")
-# ES_HIP_SO: load an alternative prebuilt kernel library (A/B experiments
-# with different -DES_DEPTH_* builds on one box; see tools/build_variants.py)
+# ES_HIP_SO: load an alternative prebuilt kernel library (A/B runs against
+# another commit's kernels on one box; see tools/build_variants.py)
 _HIP_SO = os.environ.get("ES_HIP_SO", os.path.join(_DIR, "_hip_ops.so"))
 
 _cpu_lib: Optional[ctypes.CDLL] = None

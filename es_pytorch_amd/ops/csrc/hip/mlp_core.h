@@ -11,82 +11,41 @@
 #pragma once
 #include "common.h"
 
-#ifndef ES_FP8_WIDE4
-#define ES_FP8_WIDE4 0
-#endif
-
 #define ES_MAXL 8
 #define ES_MAXDIM 2048
 
-// ES_HEAD_BATCH: the scalar-layer walks (the 256->17 action head runs here)
-// issue ES_HEAD_BT rows' weight loads into registers before the first FMA
-// of the batch, instead of one load + s_waitcnt vmcnt(0) per row (what hipcc
-// emits for the plain loop: every trip a fully exposed memory round trip on
-// a path all waves execute, with a barrier behind it). The flagship head is
-// 18/17 trips per thread -> 3 waits instead of 18. FMA order (ascending row)
-// and operands are unchanged -> bitwise-same results. 0 restores the old
-// loops.
-#ifndef ES_HEAD_BATCH
-#define ES_HEAD_BATCH 1
-#endif
+// Batch depth of the scalar-layer walks (es_walk_batched; the 256->17 action
+// head runs there): that many rows' weight loads issue into registers before
+// the first FMA of the batch, instead of the one load + s_waitcnt vmcnt(0)
+// per row that hipcc emits for a plain loop (every trip a fully exposed
+// memory round trip on a path all waves execute, with a barrier behind it).
+// The flagship head is 18/17 trips per thread -> 3 waits instead of 18.
 #define ES_HEAD_BT 8
-
-// ES_STREAM_PIPE: the steady loops of the fp8 pair forward (vec branch of
-// mlp_layers_pair_fp8) and of the pair A stream (loco_dyn_partials_pair) keep
-// their loaded rows in named register SETS that change role over an unrolled
-// loop of whole turns (forward: 2 sets of 2 row pairs, period 2; A stream: 3
-// sets of 4 rows, period 3): each sub-trip issues the loads of the free set,
-// then consumes the oldest, so there is nothing to rotate by copy and a load
-// is first waited for one (forward) or two (A stream) sub-trips after it
-// issues. (The old "next = load; consume cur; cur = next" loops compiled to
-// a copy of the just-loaded registers, hence a wait for the trip's own loads
-// at the bottom of every trip.) What it took to make the compiler keep that
-// shape: the FMAs are written as two-lane fmas (bf8_fma_pk), because the
-// vectorizer, left to find the packed form, re-orders the block and sinks a
-// sub-trip's FMAs below the next refill of their set; a sched_barrier
-// between sub-trips; one loop exit (a multi-exit loop is restructured with
-// copies on the back edge). The turn count is the block-uniform minimum; the
-// rows a lane still owns behind the ring load ahead of the drain's FMAs, so
-// no row takes a serialized tail load once the ring is in use. Per-thread
-// FMA order (ascending row into the same accumulators) and the t+e / t-e
-// roundings are unchanged -> bitwise-same results. 0 restores the old loops.
-#ifndef ES_STREAM_PIPE
-#define ES_STREAM_PIPE 1
-#endif
-// ES_STREAM_SADDR: addressing of the ring loads. 0 (default): base +
-// (int64)row * stride per lane, which the compiler strength-reduces inside
-// the ring loops to one 64-bit per-lane pointer per stream and uniform
-// steps (no v_mad_i64_i32 left in the loops). 1: a wave-uniform 64-bit base
-// in scalar registers plus one 32-bit per-lane byte offset, i.e. the
-// scalar-base form of global_load with one 32-bit vector add per load. The
-// scalar-base form measured 2% SLOWER on the flagship (6 alternated runs
-// each), so it is the knob and not the default.
-#ifndef ES_STREAM_SADDR
-#define ES_STREAM_SADDR 0
-#endif
 
 typedef uint32_t es_u32x4 __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ uint4 es_as_uint4(es_u32x4 v) {
+  uint4 w;
+  w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
+  return w;
+}
+
+// 16-B non-temporal load (the builtin wants an ext vector; HIP's uint4 is a
+// struct). For rows that exactly one block reads per step: it keeps them out
+// of L2 so the streams the whole grid shares stay resident.
+__device__ __forceinline__ uint4 es_ld16_nt(const void* p) {
+  return es_as_uint4(__builtin_nontemporal_load(reinterpret_cast<const es_u32x4*>(p)));
+}
+
 // Row-strided 16-B stream: thread reads bytes [lane, lane+16) of rows
 // row0 + k*rstep (k = 0, 1, ...) of a matrix with `rbytes` bytes per row.
-// lane < 2^32 is the caller's to guarantee (ES_MAXDIM^2 * 2 B = 8 MiB).
+// Addressing is base + (int64)row * stride per lane, which the compiler
+// strength-reduces inside the ring loops to one 64-bit per-lane pointer per
+// stream and uniform steps (no v_mad_i64_i32 left in the loops). The
+// scalar-base form of global_load (wave-uniform 64-bit base + 32-bit
+// per-lane offset) was measured 2% slower on the flagship and is gone;
+// the runs are in profiles/README.md, round 4.
 struct EsRowStream {
-#if ES_STREAM_SADDR
-  const char* ub;  // uniform base
-  uint32_t lane;   // per-lane byte offset of the cursor row
-  uint32_t sb;     // uniform bytes per k
-  __device__ __forceinline__ EsRowStream(const void* base, int row0, int rstep,
-                                         int rbytes, int lane_bytes)
-      : ub(reinterpret_cast<const char*>(base)),
-        lane((uint32_t)(row0 * rbytes + lane_bytes)),
-        sb((uint32_t)(rstep * rbytes)) {}
-  // the 32-bit sum keeps the scalar-base + 32-bit-lane-offset load form
-  // (a 64-bit sum is re-associated into a per-lane 64-bit pointer)
-  __device__ __forceinline__ const char* at(int k) const {
-    return ub + (size_t)(uint32_t)(lane + (uint32_t)k * sb);
-  }
-  __device__ __forceinline__ void advance(int k) { lane += (uint32_t)k * sb; }
-#else
   const char* lb;  // per-lane column base
   int row, rstep;
   int64_t rbytes;
@@ -98,7 +57,6 @@ struct EsRowStream {
     return lb + (int64_t)(row + k * rstep) * rbytes;
   }
   __device__ __forceinline__ void advance(int k) { row += k * rstep; }
-#endif
   __device__ __forceinline__ es_u32x4 ld(int k) const {
     return *reinterpret_cast<const es_u32x4*>(at(k));
   }
@@ -154,6 +112,37 @@ __device__ __forceinline__ void es_walk_batched(int i0, int st, int I, LD ld, FM
   }
 }
 
+// Strided row walk r = i0, i0 + st, ... < I as a depth-4 register double
+// buffer: the NEXT block's 4 loads issue before the CURRENT block's FMAs, so
+// 4-8 loads stay in flight across the loop back-edge. (hipcc alone emits one
+// load + s_waitcnt vmcnt(0) per iteration, measured ~5x slower on the HBM
+// weight stream; a plain 4-unroll still drains vmcnt to 0 at every back-edge,
+// SQ_WAIT_ANY measured at 71% of wave cycles.) ld(row) returns the loaded
+// value, whose type is ld's to choose; fma(value, row) consumes it, in
+// ascending row order. Rows behind the last full block take the plain tail.
+template <typename LD, typename FMA>
+__device__ __forceinline__ void es_walk_ring4(int i0, int st, int I, LD ld, FMA fma) {
+  int i = i0;
+  if (i + 3 * st < I) {
+    auto c0 = ld(i), c1 = ld(i + st), c2 = ld(i + 2 * st), c3 = ld(i + 3 * st);
+    for (; i + 7 * st < I; i += 4 * st) {
+      const auto n0 = ld(i + 4 * st), n1 = ld(i + 5 * st), n2 = ld(i + 6 * st),
+                 n3 = ld(i + 7 * st);
+      fma(c0, i);
+      fma(c1, i + st);
+      fma(c2, i + 2 * st);
+      fma(c3, i + 3 * st);
+      c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    }
+    fma(c0, i);
+    fma(c1, i + st);
+    fma(c2, i + 2 * st);
+    fma(c3, i + 3 * st);
+    i += 4 * st;
+  }
+  for (; i < I; i += st) fma(ld(i), i);
+}
+
 struct MlpShape {
   int n_layers;
   int dims[ES_MAXL + 1];
@@ -166,6 +155,11 @@ struct MlpShape {
 // dynamic-LDS carve sizes (bytes, 16-B aligned each; guide §6 G17)
 static inline int64_t mlp_lds_bytes(int maxdim) {
   return 2 * (int64_t)maxdim * 4 + 256 * 8 * 4;  // buf[2][maxdim] + partial
+}
+// the pair rollout kernels' carve (ES_LOCO_PAIR_CARVE): per member the two
+// activation buffers, a partial slab, the raw state (4-padded) and 64 actions
+static inline int64_t mlp_pair_lds_bytes(int maxdim, int sdim) {
+  return 2 * (mlp_lds_bytes(maxdim) + (((int64_t)sdim + 3) & ~3) * 4 + 64 * 4);
 }
 
 // Host-side shape builder; returns 0 on success.
@@ -200,12 +194,6 @@ __device__ __forceinline__ void bf8_fma(uint4 w, const float xi, float* acc) {
     acc[2 * q] = fmaf(bf2f((uint16_t)(ws[q] & 0xFFFFu)), xi, acc[2 * q]);
     acc[2 * q + 1] = fmaf(bf2f((uint16_t)(ws[q] >> 16)), xi, acc[2 * q + 1]);
   }
-}
-
-__device__ __forceinline__ uint4 es_as_uint4(es_u32x4 v) {
-  uint4 w;
-  w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-  return w;
 }
 
 // bf8_fma on accumulator PAIRS: acc2[q] = (acc[2q], acc[2q+1]). The same
@@ -245,44 +233,12 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
       for (int q = 0; q < 8; ++q) acc[q] = 0.0f;
       if (ip < PART) {
         const uint16_t* wcol = Wt + (oi << 3);
-        // Software-pipelined 4-wide register double-buffer: the NEXT block's
-        // 4 loads issue before the CURRENT block's FMAs, so ~4-8 HBM loads
-        // stay in flight across the loop back-edge. (hipcc alone emits one
-        // load + s_waitcnt vmcnt(0) per iteration — measured ~5x slower; a
-        // plain 4-unroll still drains vmcnt to 0 at every back-edge —
-        // SQ_WAIT_ANY measured at 71% of wave cycles.)
-        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-        auto ld = [&](int i) {
-          // nt: each member's weights are read by exactly one CU per step —
-          // keep them out of L2 so the shared dynamics matrix stays resident
-          u32x4v v = __builtin_nontemporal_load(
-              reinterpret_cast<const u32x4v*>(wcol + (int64_t)i * O));
-          uint4 w;
-          w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-          return w;
-        };
-        int i = ip;
-        const int step4 = PART * 4;
-        if (i + 3 * PART < I) {
-          // depth-4 register double-buffer (depth-8 raised VGPRs to 111 and
-          // cost a resident block per CU — measured net negative)
-          uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
-          for (; i + 7 * PART < I; i += step4) {
-            const uint4 n0 = ld(i + 4 * PART), n1 = ld(i + 5 * PART),
-                        n2 = ld(i + 6 * PART), n3 = ld(i + 7 * PART);
-            bf8_fma(c0, x[i], acc);
-            bf8_fma(c1, x[i + PART], acc);
-            bf8_fma(c2, x[i + 2 * PART], acc);
-            bf8_fma(c3, x[i + 3 * PART], acc);
-            c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-          }
-          bf8_fma(c0, x[i], acc);
-          bf8_fma(c1, x[i + PART], acc);
-          bf8_fma(c2, x[i + 2 * PART], acc);
-          bf8_fma(c3, x[i + 3 * PART], acc);
-          i += step4;
-        }
-        for (; i < I; i += PART) bf8_fma(ld(i), x[i], acc);
+        // depth 4: depth 8 raised VGPRs to 111 and cost a resident block per
+        // CU, measured net negative. nt: each member's weights are read by
+        // exactly one CU per step.
+        es_walk_ring4(
+            ip, PART, I, [&](int i) { return es_ld16_nt(wcol + (int64_t)i * O); },
+            [&](const uint4& w, int i) { bf8_fma(w, x[i], acc); });
 #pragma unroll
         for (int q = 0; q < 8; ++q) partial[(ip * OCT + oi) * 8 + q] = acc[q];
       }
@@ -304,25 +260,9 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
         const int oi = tid % O, ip = tid / O;
         float acc = 0.0f;
         if (ip < PART) {
-#if ES_HEAD_BATCH
           es_walk_batched<uint16_t>(
               ip, PART, I, [&](int r) { return Wt[(int64_t)r * O + oi]; },
               [&](uint16_t w, int r) { acc = fmaf(bf2f(w), x[r], acc); });
-#else
-          int i = ip;
-          const int step4 = PART * 4;
-          for (; i + 3 * PART < I; i += step4) {
-            const float w0 = bf2f(Wt[(int64_t)i * O + oi]);
-            const float w1 = bf2f(Wt[(int64_t)(i + PART) * O + oi]);
-            const float w2 = bf2f(Wt[(int64_t)(i + 2 * PART) * O + oi]);
-            const float w3 = bf2f(Wt[(int64_t)(i + 3 * PART) * O + oi]);
-            acc = fmaf(w0, x[i], acc);
-            acc = fmaf(w1, x[i + PART], acc);
-            acc = fmaf(w2, x[i + 2 * PART], acc);
-            acc = fmaf(w3, x[i + 3 * PART], acc);
-          }
-          for (; i < I; i += PART) acc = fmaf(bf2f(Wt[(int64_t)i * O + oi]), x[i], acc);
-#endif
           partial[ip * O + oi] = acc;
         }
         __syncthreads();
@@ -334,24 +274,9 @@ __device__ __forceinline__ float* mlp_layers(const uint16_t* __restrict__ wb,
       } else {
         for (int o = tid; o < O; o += nthreads) {
           float acc = bf2f(Bs[o]);
-#if ES_HEAD_BATCH
           es_walk_batched<uint16_t>(
               0, 1, I, [&](int r) { return Wt[(int64_t)r * O + o]; },
               [&](uint16_t w, int r) { acc = fmaf(bf2f(w), x[r], acc); });
-#else
-          int i = 0;
-          for (; i + 3 < I; i += 4) {
-            const float w0 = bf2f(Wt[(int64_t)i * O + o]);
-            const float w1 = bf2f(Wt[(int64_t)(i + 1) * O + o]);
-            const float w2 = bf2f(Wt[(int64_t)(i + 2) * O + o]);
-            const float w3 = bf2f(Wt[(int64_t)(i + 3) * O + o]);
-            acc = fmaf(w0, x[i], acc);
-            acc = fmaf(w1, x[i + 1], acc);
-            acc = fmaf(w2, x[i + 2], acc);
-            acc = fmaf(w3, x[i + 3], acc);
-          }
-          for (; i < I; ++i) acc = fmaf(bf2f(Wt[(int64_t)i * O + o]), x[i], acc);
-#endif
           y[o] = do_act ? tanhf(acc) : acc;
         }
       }
@@ -421,41 +346,16 @@ __device__ __forceinline__ float* mlp_layers_f32(const float* __restrict__ wb,
         for (int oi = wide ? tid : tid % QT; oi < QT; oi += nthreads) {
           float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           const float* wcol = Wt + (oi << 2);
-          // nt 16-B loads, depth-4 register double-buffer: see mlp_layers.
-          // The quad is carried as four u32 lanes exactly like the bf16
-          // octet: with a float4-typed carried value the optimizer folds
-          // the loop-carried phi(prologue load, next load) back into ONE
-          // load at the loop head, i.e. load 4 -> wait -> FMA per trip with
-          // nothing in flight across the back-edge (seen in the ISA).
-          typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-          auto ld = [&](int i) {
-            u32x4v v = __builtin_nontemporal_load(
-                reinterpret_cast<const u32x4v*>(wcol + (int64_t)i * O));
-            uint4 w;
-            w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-            return w;
-          };
-          int i = ip;
-          const int step4 = PART * 4;
-          if (i + 3 * PART < I) {
-            uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART),
-                  c3 = ld(i + 3 * PART);
-            for (; i + 7 * PART < I; i += step4) {
-              const uint4 n0 = ld(i + 4 * PART), n1 = ld(i + 5 * PART),
-                          n2 = ld(i + 6 * PART), n3 = ld(i + 7 * PART);
-              f4_fma(c0, x[i], acc);
-              f4_fma(c1, x[i + PART], acc);
-              f4_fma(c2, x[i + 2 * PART], acc);
-              f4_fma(c3, x[i + 3 * PART], acc);
-              c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-            }
-            f4_fma(c0, x[i], acc);
-            f4_fma(c1, x[i + PART], acc);
-            f4_fma(c2, x[i + 2 * PART], acc);
-            f4_fma(c3, x[i + 3 * PART], acc);
-            i += step4;
-          }
-          for (; i < I; i += PART) f4_fma(ld(i), x[i], acc);
+          // nt 16-B loads, depth-4 walk as in mlp_layers. The quad is
+          // carried as four u32 lanes exactly like the bf16 octet: with a
+          // float4-typed carried value the optimizer folds the loop-carried
+          // phi(prologue load, next load) back into ONE load at the loop
+          // head, i.e. load 4 -> wait -> FMA per trip with nothing in flight
+          // across the back-edge (seen in the ISA). Hence es_walk_ring4
+          // takes its value type from ld.
+          es_walk_ring4(
+              ip, PART, I, [&](int i) { return es_ld16_nt(wcol + (int64_t)i * O); },
+              [&](const uint4& w, int i) { f4_fma(w, x[i], acc); });
 #pragma unroll
           for (int q = 0; q < 4; ++q) partial[ip * O + (oi << 2) + q] = acc[q];
         }  // one trip unless wide: oi + nthreads >= QT
@@ -581,13 +481,8 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         const int rs2 = 2 * O;           // bytes per row pair
         const uint16_t* tcol = Tt + (oi << 3);
         const uint8_t* ecol8 = Et8 + (int64_t)ro * O + (oi << 4);
-        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
         auto lde8 = [&](int i2) {  // 16 fp8 = octet of rows 2*i2, 2*i2+1
-          u32x4v v = __builtin_nontemporal_load(
-              reinterpret_cast<const u32x4v*>(ecol8 + (int64_t)i2 * rs2));
-          uint4 w;
-          w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-          return w;
+          return es_ld16_nt(ecol8 + (int64_t)i2 * rs2);
         };
         auto ldt = [&](int r) {
           return *reinterpret_cast<const uint4*>(tcol + (int64_t)r * O);
@@ -612,14 +507,27 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
           bf8e_fma_pair(ldt(0), e8, xp[0], xm[0], accp, accm);
         }
         int i2 = ip;
-        const int step2 = PART * 2;
-#if ES_STREAM_PIPE
-        // Two 2-row-pair sets that swap role by name over a steady loop of
-        // whole turns (see ES_STREAM_PIPE): a sub-trip fills one set with
-        // the next two row pairs, then consumes the other. Every lane owns
-        // nmin or nmin + 1 row pairs; the turn count is block-uniform, and
-        // the 0..4 row pairs a lane has left behind the held set load ahead
-        // of the drain.
+        // Set ring. The loaded rows live in named register SETS that change
+        // role over an unrolled loop of whole turns (here: 2 sets of 2 row
+        // pairs, period 2): each sub-trip issues the loads of the free set,
+        // then consumes the oldest, so there is nothing to rotate by copy
+        // and a load is first waited for one sub-trip after it issues. (A
+        // "next = load; consume cur; cur = next" loop compiles to a copy of
+        // the just-loaded registers, hence a wait for the trip's own loads
+        // at the bottom of every trip.) What it takes to make the compiler
+        // keep that shape: the FMAs are written as two-lane fmas
+        // (bf8e_fma_pair_pk), because the vectorizer, left to find the
+        // packed form, re-orders the block and sinks a sub-trip's FMAs below
+        // the next refill of their set; a sched_barrier between sub-trips;
+        // one loop exit (a multi-exit loop is restructured with copies on
+        // the back edge). Every lane owns nmin or nmin + 1 row pairs; the
+        // turn count is the block-uniform minimum, and the 0..4 row pairs a
+        // lane has left behind the held set load ahead of the drain's FMAs,
+        // so no row takes a serialized tail load once the ring is in use.
+        // Per-thread FMA order (ascending row into the same accumulators)
+        // and the t+e / t-e roundings are those of the tail loop below. A
+        // 4-wide (8-row) copy-rotated pipeline was measured and lost; the
+        // numbers are in ROADMAP.md.
         const int nmin = I2 / PART;
         if (nmin >= 2) {
           const int T = (nmin - 2) >> 2;
@@ -698,65 +606,6 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
           }
           i2 = I2;  // every owned row pair is consumed
         }
-        (void)step2;
-#elif ES_FP8_WIDE4
-        // 4-wide (8 rows) pipeline: doubles the issue batch and lookahead
-        const int step4w = PART * 4;
-        if (i2 + 3 * PART < I2) {
-          uint4 e0 = lde8(i2), e1 = lde8(i2 + PART), e2 = lde8(i2 + 2 * PART),
-                e3 = lde8(i2 + 3 * PART);
-          uint4 t00 = ldt(ro + 2 * i2), t01 = ldt(ro + 2 * i2 + 1);
-          uint4 t10 = ldt(ro + 2 * (i2 + PART)), t11 = ldt(ro + 2 * (i2 + PART) + 1);
-          uint4 t20 = ldt(ro + 2 * (i2 + 2 * PART)), t21 = ldt(ro + 2 * (i2 + 2 * PART) + 1);
-          uint4 t30 = ldt(ro + 2 * (i2 + 3 * PART)), t31 = ldt(ro + 2 * (i2 + 3 * PART) + 1);
-          for (; i2 + 7 * PART < I2; i2 += step4w) {
-            const uint4 ne0 = lde8(i2 + 4 * PART), ne1 = lde8(i2 + 5 * PART),
-                        ne2 = lde8(i2 + 6 * PART), ne3 = lde8(i2 + 7 * PART);
-            const uint4 nt00 = ldt(ro + 2 * (i2 + 4 * PART)),
-                        nt01 = ldt(ro + 2 * (i2 + 4 * PART) + 1),
-                        nt10 = ldt(ro + 2 * (i2 + 5 * PART)),
-                        nt11 = ldt(ro + 2 * (i2 + 5 * PART) + 1),
-                        nt20 = ldt(ro + 2 * (i2 + 6 * PART)),
-                        nt21 = ldt(ro + 2 * (i2 + 6 * PART) + 1),
-                        nt30 = ldt(ro + 2 * (i2 + 7 * PART)),
-                        nt31 = ldt(ro + 2 * (i2 + 7 * PART) + 1);
-            fma_pairblk(e0, t00, t01, ro + 2 * i2);
-            fma_pairblk(e1, t10, t11, ro + 2 * (i2 + PART));
-            fma_pairblk(e2, t20, t21, ro + 2 * (i2 + 2 * PART));
-            fma_pairblk(e3, t30, t31, ro + 2 * (i2 + 3 * PART));
-            e0 = ne0; e1 = ne1; e2 = ne2; e3 = ne3;
-            t00 = nt00; t01 = nt01; t10 = nt10; t11 = nt11;
-            t20 = nt20; t21 = nt21; t30 = nt30; t31 = nt31;
-          }
-          fma_pairblk(e0, t00, t01, ro + 2 * i2);
-          fma_pairblk(e1, t10, t11, ro + 2 * (i2 + PART));
-          fma_pairblk(e2, t20, t21, ro + 2 * (i2 + 2 * PART));
-          fma_pairblk(e3, t30, t31, ro + 2 * (i2 + 3 * PART));
-          i2 += step4w;
-        }
-#else
-        if (i2 + PART < I2) {
-          // 2-wide (4 rows) software-pipelined double buffer, mirroring the
-          // bf16 path's issue batching at the same register footprint
-          uint4 e0 = lde8(i2), e1 = lde8(i2 + PART);
-          uint4 t00 = ldt(ro + 2 * i2), t01 = ldt(ro + 2 * i2 + 1);
-          uint4 t10 = ldt(ro + 2 * (i2 + PART)), t11 = ldt(ro + 2 * (i2 + PART) + 1);
-          for (; i2 + 3 * PART < I2; i2 += step2) {
-            const uint4 ne0 = lde8(i2 + 2 * PART), ne1 = lde8(i2 + 3 * PART);
-            const uint4 nt00 = ldt(ro + 2 * (i2 + 2 * PART)),
-                        nt01 = ldt(ro + 2 * (i2 + 2 * PART) + 1),
-                        nt10 = ldt(ro + 2 * (i2 + 3 * PART)),
-                        nt11 = ldt(ro + 2 * (i2 + 3 * PART) + 1);
-            fma_pairblk(e0, t00, t01, ro + 2 * i2);
-            fma_pairblk(e1, t10, t11, ro + 2 * (i2 + PART));
-            e0 = ne0; e1 = ne1;
-            t00 = nt00; t01 = nt01; t10 = nt10; t11 = nt11;
-          }
-          fma_pairblk(e0, t00, t01, ro + 2 * i2);
-          fma_pairblk(e1, t10, t11, ro + 2 * (i2 + PART));
-          i2 += step2;
-        }
-#endif
         for (; i2 < I2; i2 += PART)
           fma_pairblk(lde8(i2), ldt(ro + 2 * i2), ldt(ro + 2 * i2 + 1), ro + 2 * i2);
 #pragma unroll
@@ -784,7 +633,6 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         const int oi = tid % O, ip = tid / O;
         float accp = 0.0f, accm = 0.0f;
         if (ip < PART) {
-#if ES_HEAD_BATCH
           es_walk_batched<EsTE8>(
               ip, PART, I,
               [&](int r) {
@@ -795,14 +643,6 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
                 accp = fmaf(tw + ew, xp[r], accp);
                 accm = fmaf(tw - ew, xm[r], accm);
               });
-#else
-          for (int i = ip; i < I; i += PART) {
-            const float tw = bf2f(Tt[(int64_t)i * O + oi]);
-            const float ew = fp8_byte(Et8[(int64_t)i * O + oi]);
-            accp = fmaf(tw + ew, xp[i], accp);
-            accm = fmaf(tw - ew, xm[i], accm);
-          }
-#endif
           partial[ip * O + oi] = accp;
           partm[ip * O + oi] = accm;
         }
@@ -821,7 +661,6 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         for (int o = tid; o < O; o += nthreads) {
           const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
           float accp = tB + eB, accm = tB - eB;
-#if ES_HEAD_BATCH
           es_walk_batched<EsTE8>(
               0, 1, I,
               [&](int r) {
@@ -832,14 +671,6 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
                 accp = fmaf(tw + ew, xp[r], accp);
                 accm = fmaf(tw - ew, xm[r], accm);
               });
-#else
-          for (int i = 0; i < I; ++i) {
-            const float tw = bf2f(Tt[(int64_t)i * O + o]);
-            const float ew = fp8_byte(Et8[(int64_t)i * O + o]);
-            accp = fmaf(tw + ew, xp[i], accp);
-            accm = fmaf(tw - ew, xm[i], accm);
-          }
-#endif
           yp[o] = do_act ? tanhf(accp) : accp;
           ym[o] = do_act ? tanhf(accm) : accm;
         }
@@ -919,19 +750,15 @@ __device__ __forceinline__ void mlp_layers_pair(
       if (ip < PART) {
         const uint16_t* tcol = Tt + (oi << 3);
         const uint16_t* ecol = Et + (oi << 3);
-        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
         // eps rows are touched by exactly one block -> nt; theta is shared
         // by the whole grid -> regular load, stays L2/MALL-resident
-        auto lde = [&](int i) {
-          u32x4v v = __builtin_nontemporal_load(
-              reinterpret_cast<const u32x4v*>(ecol + (int64_t)i * O));
-          uint4 w;
-          w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-          return w;
-        };
+        auto lde = [&](int i) { return es_ld16_nt(ecol + (int64_t)i * O); };
         auto ldt = [&](int i) {
           return *reinterpret_cast<const uint4*>(tcol + (int64_t)i * O);
         };
+        // es_walk_ring4 written out: it loads four theta, then four eps, and
+        // the helper's one-value-per-row ld would bundle them per row, which
+        // is a different kernel (118 instead of 168 VGPRs; see ROADMAP.md)
         int i = ip;
         const int step4 = PART * 4;
         if (i + 3 * PART < I) {
@@ -984,7 +811,6 @@ __device__ __forceinline__ void mlp_layers_pair(
         const int oi = tid % O, ip = tid / O;
         float accp = 0.0f, accm = 0.0f;
         if (ip < PART) {
-#if ES_HEAD_BATCH
           es_walk_batched<EsTE16>(
               ip, PART, I,
               [&](int r) {
@@ -995,14 +821,6 @@ __device__ __forceinline__ void mlp_layers_pair(
                 accp = fmaf(tw + ew, xp[r], accp);
                 accm = fmaf(tw - ew, xm[r], accm);
               });
-#else
-          for (int i = ip; i < I; i += PART) {
-            const float tw = bf2f(Tt[(int64_t)i * O + oi]);
-            const float ew = bf2f(Et[(int64_t)i * O + oi]);
-            accp = fmaf(tw + ew, xp[i], accp);
-            accm = fmaf(tw - ew, xm[i], accm);
-          }
-#endif
           partial[ip * O + oi] = accp;
           partm[ip * O + oi] = accm;
         }
@@ -1021,7 +839,6 @@ __device__ __forceinline__ void mlp_layers_pair(
         for (int o = tid; o < O; o += nthreads) {
           const float tB = bf2f(TBs[o]), eB = bf2f(EBs[o]);
           float accp = tB + eB, accm = tB - eB;
-#if ES_HEAD_BATCH
           es_walk_batched<EsTE16>(
               0, 1, I,
               [&](int r) {
@@ -1032,14 +849,6 @@ __device__ __forceinline__ void mlp_layers_pair(
                 accp = fmaf(tw + ew, xp[r], accp);
                 accm = fmaf(tw - ew, xm[r], accm);
               });
-#else
-          for (int i = 0; i < I; ++i) {
-            const float tw = bf2f(Tt[(int64_t)i * O + o]);
-            const float ew = bf2f(Et[(int64_t)i * O + o]);
-            accp = fmaf(tw + ew, xp[i], accp);
-            accm = fmaf(tw - ew, xm[i], accm);
-          }
-#endif
           yp[o] = do_act ? tanhf(accp) : accp;
           ym[o] = do_act ? tanhf(accm) : accm;
         }

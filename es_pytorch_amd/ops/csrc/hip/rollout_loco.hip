@@ -19,15 +19,6 @@
 //    straggler block measured ~15-20% tail on every step).
 #include "mlp_core.h"
 
-// ES_DYN_DEPTH8: 8-deep lookahead on the shared-A L2 stream (12 uint4 live
-// instead of 8). Measured -4.3% same-box on the fp8 flagship (66.9 ->
-// 64.1-64.4 us/step); the fp8 kernel lands at 123 VGPRs (4 waves kept) and
-// the bf16 pair kernel stays 168 (its peak is in the forward). Default ON;
-// accumulation order (ascending i) unchanged -> bitwise-same results.
-#ifndef ES_DYN_DEPTH8
-#define ES_DYN_DEPTH8 1
-#endif
-
 struct LocoArgs {
   int S;               // latent state dim
   int A;               // action dim
@@ -72,16 +63,12 @@ __device__ __forceinline__ void loco_build_obs(
   }
 }
 
-// ES_PAIR_OBS: one obs pass for both members of a pair — obmean/obstd are
-// loaded once and both members' state loads issue together (0: two
-// one-member passes). Same per-member arithmetic, division included.
-#ifndef ES_PAIR_OBS
-#define ES_PAIR_OBS 1
-#endif
+// One obs pass for both members of a pair: obmean/obstd are loaded once and
+// both members' state loads issue together. Same per-member arithmetic as
+// loco_build_obs, division included.
 __device__ __forceinline__ void loco_build_obs_pair(
     const LocoArgs& la, const LocoPtrs& P, int bp, int bm, float* bufAp, float* bufAm,
     float* rawsP, float* rawsM, int tid, int nth) {
-#if ES_PAIR_OBS
   const int S = la.S;
   const float* sp = P.s_glob + (int64_t)bp * S;
   const float* sm = P.s_glob + (int64_t)bm * S;
@@ -100,10 +87,6 @@ __device__ __forceinline__ void loco_build_obs_pair(
     bufAp[S + tid] = fclampf((relp - mean) / sd, -la.ob_clip, la.ob_clip);
     bufAm[S + tid] = fclampf((relm - mean) / sd, -la.ob_clip, la.ob_clip);
   }
-#else
-  loco_build_obs(la, P, bp, bufAp, rawsP, tid, nth);
-  loco_build_obs(la, P, bm, bufAm, rawsM, tid, nth);
-#endif
 }
 
 // ---- net output -> clamped env action for slot b (modes 0/1/2/3) ---------
@@ -181,8 +164,12 @@ __device__ __forceinline__ void loco_dyn_partials(
     };
     int i = ip;
     const int step4 = PART * 4;
-#if ES_DYN_DEPTH8
-    // 8-deep lookahead on the L2 A stream (see loco_dyn_partials_pair)
+    // 8-deep lookahead on the shared-A L2 stream (12 uint4 live instead of
+    // the 8 of a depth-4 walk; measured -4.3% us/step on the fp8 flagship
+    // when the pair kernels got it). Accumulation order stays ascending i.
+    // Written out here and in loco_dyn_partials_pair<false>, not shared like
+    // es_walk_ring4: with the FMA behind a lambda loco_step_kernel goes from
+    // 91 to 107 VGPRs (5 -> 4 waves).
     if (i + 7 * PART < S) {
       uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
       uint4 d0 = ld(i + 4 * PART), d1 = ld(i + 5 * PART), d2 = ld(i + 6 * PART),
@@ -207,25 +194,6 @@ __device__ __forceinline__ void loco_dyn_partials(
       if (i + 7 * PART < S) bf8_fma(d3, raws[i + 7 * PART], acc);
       i += 8 * PART;
     }
-#else
-    if (i + 3 * PART < S) {
-      uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
-      for (; i + 7 * PART < S; i += step4) {
-        const uint4 n0 = ld(i + 4 * PART), n1 = ld(i + 5 * PART),
-                    n2 = ld(i + 6 * PART), n3 = ld(i + 7 * PART);
-        bf8_fma(c0, raws[i], acc);
-        bf8_fma(c1, raws[i + PART], acc);
-        bf8_fma(c2, raws[i + 2 * PART], acc);
-        bf8_fma(c3, raws[i + 3 * PART], acc);
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-      }
-      bf8_fma(c0, raws[i], acc);
-      bf8_fma(c1, raws[i + PART], acc);
-      bf8_fma(c2, raws[i + 2 * PART], acc);
-      bf8_fma(c3, raws[i + 3 * PART], acc);
-      i += step4;
-    }
-#endif
     for (; i < S; i += PART) bf8_fma(ld(i), raws[i], acc);
 #pragma unroll
     for (int q = 0; q < 8; ++q) partial[(ip * OCT + oi) * 8 + q] = acc[q];
@@ -459,60 +427,51 @@ __device__ __forceinline__ void loco_dyn_finish(
   loco_dyn_finish_n<1>(la, P, bs, rs, as, ps, tid, nth);
 }
 
-// ES_PAIR_FINISH: one fused epilogue for both members of a pair (0: two
-// one-member calls, one after the other).
-#ifndef ES_PAIR_FINISH
-#define ES_PAIR_FINISH 1
-#endif
+// One fused epilogue for both members of a pair.
 __device__ __forceinline__ void loco_dyn_finish_pair(
     const LocoArgs& la, const LocoPtrs& P, int bp, int bm, const float* rawsP,
     const float* rawsM, const float* abufP, const float* abufM, float* partP,
     float* partM, int tid, int nth) {
-#if ES_PAIR_FINISH
   const int bs[2] = {bp, bm};
   const float* const rs[2] = {rawsP, rawsM};
   const float* const as[2] = {abufP, abufM};
   float* const ps[2] = {partP, partM};
   loco_dyn_finish_n<2>(la, P, bs, rs, as, ps, tid, nth);
-#else
-  loco_dyn_finish(la, P, bp, rawsP, abufP, partP, tid, nth);
-  loco_dyn_finish(la, P, bm, rawsM, abufM, partM, tid, nth);
-#endif
 }
 
 template <typename WT = uint16_t>
 __device__ __forceinline__ void loco_step_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P, int b, uint64_t salt,
-    float* bufA, float* bufB, float* partial, float* raws, float* abuf, float* sc) {
+    float* bufA, float* bufB, float* partial, float* raws, float* abuf) {
   loco_fwd_body<WT>(sh, la, P, b, salt, bufA, bufB, partial, raws, abuf);
   if (la.S % 8 == 0)
     loco_dyn_partials(P.Am, la.S, raws, partial, threadIdx.x, blockDim.x);
   loco_dyn_finish(la, P, b, raws, abuf, partial, threadIdx.x, blockDim.x);
 }
 
-#define ES_LOCO_CARVE()                                          \
+// NTH = block size: the partial slab is NTH * 8 floats
+#define ES_LOCO_CARVE(NTH)                                       \
   extern __shared__ __attribute__((aligned(16))) char smem[];    \
   float* bufA = reinterpret_cast<float*>(smem);                  \
   float* bufB = bufA + sh.maxdim;                                \
   float* partial = bufB + sh.maxdim;                             \
-  float* raws = partial + 256 * 8;                               \
-  float* abuf = raws + ((la.S + 3) & ~3);                        \
-  float* sc = abuf + 64;
+  float* raws = partial + (NTH) * 8;                             \
+  float* abuf = raws + ((la.S + 3) & ~3);
 
 __global__ void __launch_bounds__(256)
 loco_step_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, uint64_t salt) {
-  ES_LOCO_CARVE();
-  loco_step_body(sh, la, P, blockIdx.x, salt, bufA, bufB, partial, raws, abuf, sc);
+  ES_LOCO_CARVE(256);
+  loco_step_body(sh, la, P, blockIdx.x, salt, bufA, bufB, partial, raws, abuf);
 }
 
 __global__ void __launch_bounds__(256)
 loco_episode_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base, int n_steps,
                     int salt_base) {
-  ES_LOCO_CARVE();
+  ES_LOCO_CARVE(256);
   const int b = member_base + blockIdx.x;
   for (int t = 1; t <= n_steps; ++t)
     loco_step_body(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial, raws,
-                   abuf, sc);
+                   abuf);
 }
 
 // 512-thread variant for the LATENCY-BOUND noiseless side episode: one
@@ -523,17 +482,11 @@ loco_episode_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base, int n
 __global__ void __launch_bounds__(512)
 loco_episode512_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
                        int n_steps, int salt_base) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* bufA = reinterpret_cast<float*>(smem);
-  float* bufB = bufA + sh.maxdim;
-  float* partial = bufB + sh.maxdim;
-  float* raws = partial + 512 * 8;
-  float* abuf = raws + ((la.S + 3) & ~3);
-  float* sc = abuf + 64;
+  ES_LOCO_CARVE(512);
   const int b = member_base + blockIdx.x;
   for (int t = 1; t <= n_steps; ++t)
     loco_step_body(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial, raws,
-                   abuf, sc);
+                   abuf);
 }
 
 // ---- fp32-weights variants (weights_dtype = "fp32") ------------------------
@@ -544,34 +497,28 @@ loco_episode512_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
 // ES_MAXDIM = 256 * 8 floats when a layer is wider than 4 * nthreads.
 __global__ void __launch_bounds__(256)
 loco_step_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, uint64_t salt) {
-  ES_LOCO_CARVE();
-  loco_step_body<float>(sh, la, P, blockIdx.x, salt, bufA, bufB, partial, raws, abuf, sc);
+  ES_LOCO_CARVE(256);
+  loco_step_body<float>(sh, la, P, blockIdx.x, salt, bufA, bufB, partial, raws, abuf);
 }
 
 __global__ void __launch_bounds__(256)
 loco_episode_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
                         int n_steps, int salt_base) {
-  ES_LOCO_CARVE();
+  ES_LOCO_CARVE(256);
   const int b = member_base + blockIdx.x;
   for (int t = 1; t <= n_steps; ++t)
     loco_step_body<float>(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial,
-                          raws, abuf, sc);
+                          raws, abuf);
 }
 
 __global__ void __launch_bounds__(512)
 loco_episode512_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base,
                            int n_steps, int salt_base) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* bufA = reinterpret_cast<float*>(smem);
-  float* bufB = bufA + sh.maxdim;
-  float* partial = bufB + sh.maxdim;
-  float* raws = partial + 512 * 8;
-  float* abuf = raws + ((la.S + 3) & ~3);
-  float* sc = abuf + 64;
+  ES_LOCO_CARVE(512);
   const int b = member_base + blockIdx.x;
   for (int t = 1; t <= n_steps; ++t)
     loco_step_body<float>(sh, la, P, b, (uint64_t)(salt_base + t), bufA, bufB, partial,
-                          raws, abuf, sc);
+                          raws, abuf);
 }
 
 // ---- split-dynamics path ---------------------------------------------------
@@ -590,8 +537,7 @@ loco_episode512_f32_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, int member_base
 //                      trajectories match bitwise.
 __global__ void __launch_bounds__(256)
 loco_fwd_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, uint64_t salt, float* act_glob) {
-  ES_LOCO_CARVE();
-  (void)sc;
+  ES_LOCO_CARVE(256);
   const int b = blockIdx.x;
   loco_fwd_body(sh, la, P, b, salt, bufA, bufB, partial, raws, abuf);
   if (threadIdx.x < la.A) act_glob[(int64_t)b * 64 + threadIdx.x] = abuf[threadIdx.x];
@@ -639,26 +585,7 @@ loco_dyn_kernel(LocoArgs la, LocoPtrs P, const float* act_glob, int n_pop) {
 #pragma unroll
       for (int g = 0; g < G; ++g) bf8_fma(c, raws[g * Spad + i], acc[g]);
     };
-    int i = ip;
-    const int step4 = PART * 4;
-    if (i + 3 * PART < S) {
-      uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
-      for (; i + 7 * PART < S; i += step4) {
-        const uint4 n0 = ld(i + 4 * PART), n1 = ld(i + 5 * PART),
-                    n2 = ld(i + 6 * PART), n3 = ld(i + 7 * PART);
-        fmaG(c0, i);
-        fmaG(c1, i + PART);
-        fmaG(c2, i + 2 * PART);
-        fmaG(c3, i + 3 * PART);
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-      }
-      fmaG(c0, i);
-      fmaG(c1, i + PART);
-      fmaG(c2, i + 2 * PART);
-      fmaG(c3, i + 3 * PART);
-      i += step4;
-    }
-    for (; i < S; i += PART) fmaG(ld(i), i);
+    es_walk_ring4(ip, PART, S, ld, fmaG);
 #pragma unroll
     for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -694,9 +621,10 @@ static int loco_launch_dyn(const LocoArgs& la, const LocoPtrs& P, const float* a
 // Effective weights are bf16(theta) +- bf16(sigma*eps) (two roundings); with
 // sigma = 0 the trajectories are BITWISE-identical to es_loco_step.
 
-// PIPE = false keeps the ES_DYN_DEPTH8 loop whatever ES_STREAM_PIPE says: the
-// whole-episode kernel runs under a 128-VGPR bound with spills, and the set
-// ring adds to them.
+// A-matvec partial sums for both members of a pair off one A stream. PIPE =
+// true streams A through the set ring; PIPE = false keeps the 8-deep
+// copy-rotated walk of loco_dyn_partials: the whole-episode kernel runs under
+// a 128-VGPR bound with spills, and the set ring adds to them.
 template <bool PIPE = true>
 __device__ __forceinline__ void loco_dyn_partials_pair(
     const uint16_t* Am, int S, const float* rawsP, const float* rawsM,
@@ -717,124 +645,104 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
       bf8_fma(c, rawsM[i], accm);
     };
     int i = ip;
-    const int step4 = PART * 4;
-    constexpr bool kPipe = PIPE && ES_STREAM_PIPE;
-    if constexpr (kPipe) {
-    // Three 4-row sets that change role by name over a steady loop of
-    // whole turns (see ES_STREAM_PIPE, mlp_core.h): each sub-trip fills the
-    // free set 8 rows ahead, then consumes the oldest. Every lane owns nmin
-    // or nmin + 1 rows; the turn count is block-uniform, and the 0..12 rows
-    // a lane has left behind the two held sets load ahead of the drain.
-    const int nmin = S / PART;
-    if (nmin >= 8) {
-      const int T = (nmin - 8) / 12;
-      const int rem = (S - 1 - ip) / PART + 1 - 12 * T - 8;
-      EsRowStream as(Am, ip, PART, 2 * S, oi << 4);
-      const float* xP = rawsP + ip;
-      const float* xM = rawsM + ip;
-      es_f32x2 a2p[4], a2m[4];
+    if constexpr (PIPE) {
+      // Set ring (design note at the ring in mlp_layers_pair_fp8,
+      // mlp_core.h): three 4-row sets that change role by name over a steady
+      // loop of whole turns; each sub-trip fills the free set 8 rows ahead,
+      // then consumes the oldest, so a load is first waited for two
+      // sub-trips after it issues. Every lane owns nmin or nmin + 1 rows;
+      // the turn count is block-uniform, and the 0..12 rows a lane has left
+      // behind the two held sets load ahead of the drain.
+      const int nmin = S / PART;
+      if (nmin >= 8) {
+        const int T = (nmin - 8) / 12;
+        const int rem = (S - 1 - ip) / PART + 1 - 12 * T - 8;
+        EsRowStream as(Am, ip, PART, 2 * S, oi << 4);
+        const float* xP = rawsP + ip;
+        const float* xM = rawsM + ip;
+        es_f32x2 a2p[4], a2m[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) a2p[q] = a2m[q] = es_f32x2{0.0f, 0.0f};
-      struct Set { es_u32x4 v[4]; };
-      auto fill = [&](Set& s) {
+        for (int q = 0; q < 4; ++q) a2p[q] = a2m[q] = es_f32x2{0.0f, 0.0f};
+        struct Set { es_u32x4 v[4]; };
+        auto fill = [&](Set& s) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) s.v[k] = as.ld(k);
-        as.advance(4);
-      };
-      auto eat = [&](const Set& s) {
+          for (int k = 0; k < 4; ++k) s.v[k] = as.ld(k);
+          as.advance(4);
+        };
+        auto eat = [&](const Set& s) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          bf8_fma_pk(s.v[k], xP[k * PART], a2p);
-          bf8_fma_pk(s.v[k], xM[k * PART], a2m);
+          for (int k = 0; k < 4; ++k) {
+            bf8_fma_pk(s.v[k], xP[k * PART], a2p);
+            bf8_fma_pk(s.v[k], xM[k * PART], a2m);
+          }
+          xP += 4 * PART;
+          xM += 4 * PART;
+        };
+        Set c, d, n;
+        fill(c);
+        fill(d);
+        // the fences keep a sub-trip's work out of the next one, where the
+        // set it reads is refilled
+        for (int t = T; t > 0; --t) {
+          fill(n); eat(c);
+          __builtin_amdgcn_sched_barrier(0);
+          fill(c); eat(d);
+          __builtin_amdgcn_sched_barrier(0);
+          fill(d); eat(n);
+          __builtin_amdgcn_sched_barrier(0);
         }
-        xP += 4 * PART;
-        xM += 4 * PART;
-      };
-      Set c, d, n;
-      fill(c);
-      fill(d);
-      // the fences keep a sub-trip's work out of the next one, where the
-      // set it reads is refilled
-      for (int t = T; t > 0; --t) {
-        fill(n); eat(c);
-        __builtin_amdgcn_sched_barrier(0);
-        fill(c); eat(d);
-        __builtin_amdgcn_sched_barrier(0);
-        fill(d); eat(n);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      // drain: the rows left load into fresh names (merging with a set's
-      // stale rows would copy them), then c, d and they are consumed
-      es_u32x4 f[12];
+        // drain: the rows left load into fresh names (merging with a set's
+        // stale rows would copy them), then c, d and they are consumed
+        es_u32x4 f[12];
 #pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k < rem) f[k] = as.ld(k);
-      __builtin_amdgcn_sched_barrier(0);
-      eat(c);
-      __builtin_amdgcn_sched_barrier(0);
-      eat(d);
-      __builtin_amdgcn_sched_barrier(0);
+        for (int k = 0; k < 12; ++k)
+          if (k < rem) f[k] = as.ld(k);
+        __builtin_amdgcn_sched_barrier(0);
+        eat(c);
+        __builtin_amdgcn_sched_barrier(0);
+        eat(d);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        if (k < rem) {
-          bf8_fma_pk(f[k], xP[k * PART], a2p);
-          bf8_fma_pk(f[k], xM[k * PART], a2m);
+        for (int k = 0; k < 12; ++k) {
+          if (k < rem) {
+            bf8_fma_pk(f[k], xP[k * PART], a2p);
+            bf8_fma_pk(f[k], xM[k * PART], a2m);
+          }
         }
-      }
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        accp[2 * q] = a2p[q].x; accp[2 * q + 1] = a2p[q].y;
-        accm[2 * q] = a2m[q].x; accm[2 * q + 1] = a2m[q].y;
+        for (int q = 0; q < 4; ++q) {
+          accp[2 * q] = a2p[q].x; accp[2 * q + 1] = a2p[q].y;
+          accm[2 * q] = a2m[q].x; accm[2 * q + 1] = a2m[q].y;
+        }
+        i = S;  // every owned row is consumed
       }
-      i = S;  // every owned row is consumed
-    }
-    }
-    if constexpr (!kPipe) {
-#if ES_DYN_DEPTH8
-    if (i + 7 * PART < S) {
-      uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
-      uint4 d0 = ld(i + 4 * PART), d1 = ld(i + 5 * PART), d2 = ld(i + 6 * PART),
-            d3 = ld(i + 7 * PART);
-      for (; i + 11 * PART < S; i += step4) {
-        const uint4 n0 = ld(i + 8 * PART), n1 = ld(i + 9 * PART),
-                    n2 = ld(i + 10 * PART), n3 = ld(i + 11 * PART);
-        fma2(c0, i);
-        fma2(c1, i + PART);
-        fma2(c2, i + 2 * PART);
-        fma2(c3, i + 3 * PART);
-        c0 = d0; c1 = d1; c2 = d2; c3 = d3;
-        d0 = n0; d1 = n1; d2 = n2; d3 = n3;
+    } else {
+      const int step4 = PART * 4;
+      if (i + 7 * PART < S) {
+        uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
+        uint4 d0 = ld(i + 4 * PART), d1 = ld(i + 5 * PART), d2 = ld(i + 6 * PART),
+              d3 = ld(i + 7 * PART);
+        for (; i + 11 * PART < S; i += step4) {
+          const uint4 n0 = ld(i + 8 * PART), n1 = ld(i + 9 * PART),
+                      n2 = ld(i + 10 * PART), n3 = ld(i + 11 * PART);
+          fma2(c0, i);
+          fma2(c1, i + PART);
+          fma2(c2, i + 2 * PART);
+          fma2(c3, i + 3 * PART);
+          c0 = d0; c1 = d1; c2 = d2; c3 = d3;
+          d0 = n0; d1 = n1; d2 = n2; d3 = n3;
+        }
+        // drain the 8 preloaded blocks (guarded; order stays ascending)
+        if (i < S) fma2(c0, i);
+        if (i + PART < S) fma2(c1, i + PART);
+        if (i + 2 * PART < S) fma2(c2, i + 2 * PART);
+        if (i + 3 * PART < S) fma2(c3, i + 3 * PART);
+        if (i + 4 * PART < S) fma2(d0, i + 4 * PART);
+        if (i + 5 * PART < S) fma2(d1, i + 5 * PART);
+        if (i + 6 * PART < S) fma2(d2, i + 6 * PART);
+        if (i + 7 * PART < S) fma2(d3, i + 7 * PART);
+        i += 8 * PART;
       }
-      // drain the 8 preloaded blocks (guarded; order stays ascending)
-      if (i < S) fma2(c0, i);
-      if (i + PART < S) fma2(c1, i + PART);
-      if (i + 2 * PART < S) fma2(c2, i + 2 * PART);
-      if (i + 3 * PART < S) fma2(c3, i + 3 * PART);
-      if (i + 4 * PART < S) fma2(d0, i + 4 * PART);
-      if (i + 5 * PART < S) fma2(d1, i + 5 * PART);
-      if (i + 6 * PART < S) fma2(d2, i + 6 * PART);
-      if (i + 7 * PART < S) fma2(d3, i + 7 * PART);
-      i += 8 * PART;
-    }
-#else
-    if (i + 3 * PART < S) {
-      uint4 c0 = ld(i), c1 = ld(i + PART), c2 = ld(i + 2 * PART), c3 = ld(i + 3 * PART);
-      for (; i + 7 * PART < S; i += step4) {
-        const uint4 n0 = ld(i + 4 * PART), n1 = ld(i + 5 * PART),
-                    n2 = ld(i + 6 * PART), n3 = ld(i + 7 * PART);
-        fma2(c0, i);
-        fma2(c1, i + PART);
-        fma2(c2, i + 2 * PART);
-        fma2(c3, i + 3 * PART);
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-      }
-      fma2(c0, i);
-      fma2(c1, i + PART);
-      fma2(c2, i + 2 * PART);
-      fma2(c3, i + 3 * PART);
-      i += step4;
-    }
-#endif
     }
     for (; i < S; i += PART) fma2(ld(i), i);
 #pragma unroll
@@ -846,31 +754,16 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
   __syncthreads();
 }
 
-// ES_DYN_EARLY (experiment knob): compute the A-matvec partials BEFORE the
-// policy forward, into a dedicated LDS slab — the A sweep needs only the
-// raw state, so its L2 latency then overlaps the forward's HBM weight
-// streaming deterministically within the block (instead of statistically
-// across blocks). Costs 16 KB LDS per block (one resident block at fp8's
-// 4-block occupancy); which wins is measured.
-#ifndef ES_DYN_EARLY
-#define ES_DYN_EARLY 0
-#endif
-
 // EB = uint16_t (bf16 eps rows) or uint8_t (fp8 row-pair-interleaved rows)
 template <typename EB, bool PIPE = true>
 __device__ __forceinline__ void loco_pair_step_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P,
     const uint16_t* tb, const EB* eb, int bp, int bm, uint64_t salt,
     float* bufAp, float* bufAm, float* bufBp, float* bufBm, float* partial,
-    float* rawsP, float* rawsM, float* abufP, float* abufM,
-    float* partA = nullptr) {
+    float* rawsP, float* rawsM, float* abufP, float* abufM) {
   const int tid = threadIdx.x, nth = blockDim.x;
   loco_build_obs_pair(la, P, bp, bm, bufAp, bufAm, rawsP, rawsM, tid, nth);
   __syncthreads();
-  const bool early = ES_DYN_EARLY && partA != nullptr && la.S % 8 == 0;
-  if (early)
-    loco_dyn_partials_pair<PIPE>(P.Am, la.S, rawsP, rawsM, partA, partA + 2048,
-                           tid, nth);
   float *ap, *am;
   if constexpr (sizeof(EB) == 1)
     mlp_layers_pair_fp8(tb, (const uint8_t*)eb, sh, bufAp, bufAm, bufBp, bufBm,
@@ -881,12 +774,11 @@ __device__ __forceinline__ void loco_pair_step_body(
   loco_decode_action(sh, la, P, bp, salt, ap, abufP, tid);
   loco_decode_action(sh, la, P, bm, salt, am, abufM, tid);
   __syncthreads();
-  float* pd = early ? partA : partial;
-  if (!early && la.S % 8 == 0)
+  if (la.S % 8 == 0)
     loco_dyn_partials_pair<PIPE>(P.Am, la.S, rawsP, rawsM, partial, partial + 2048,
-                           tid, nth);
-  loco_dyn_finish_pair(la, P, bp, bm, rawsP, rawsM, abufP, abufM, pd, pd + 2048, tid,
-                       nth);
+                                 tid, nth);
+  loco_dyn_finish_pair(la, P, bp, bm, rawsP, rawsM, abufP, abufM, partial,
+                       partial + 2048, tid, nth);
 }
 
 #define ES_LOCO_PAIR_CARVE()                                     \
@@ -900,32 +792,26 @@ __device__ __forceinline__ void loco_pair_step_body(
   float* rawsM = rawsP + ((la.S + 3) & ~3);                      \
   float* abufP = rawsM + ((la.S + 3) & ~3);                      \
   float* abufM = abufP + 64;                                     \
-  float* partA = ES_DYN_EARLY ? abufM + 64 : nullptr;            \
   const int q = blockIdx.x;                                      \
   const int p = q / la.eps, e = q % la.eps;                      \
   const int bp = p * la.eps + e;                                 \
   const int bm = (n_pairs + p) * la.eps + e;                     \
   const auto* ebp = eb + (int64_t)p * la.row_stride;
 
-// ES_PAIR_MINWAVES (experiment knob): force a min-waves/SIMD bound on the
-// pair step kernel so deeper rings can be capped to 3 waves (168 VGPRs)
-#ifndef ES_PAIR_MINWAVES
-#define ES_PAIR_MINWAVES 1
-#endif
-__global__ void __launch_bounds__(256, ES_PAIR_MINWAVES)
+__global__ void __launch_bounds__(256, 1)
 loco_pair_step_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* tb,
                       const uint16_t* eb, int n_pairs, uint64_t salt) {
   ES_LOCO_PAIR_CARVE();
   loco_pair_step_body(sh, la, P, tb, ebp, bp, bm, salt, bufAp, bufAm, bufBp, bufBm,
-                      partial, rawsP, rawsM, abufP, abufM, partA);
+                      partial, rawsP, rawsM, abufP, abufM);
 }
 
-__global__ void __launch_bounds__(256, ES_PAIR_MINWAVES)
+__global__ void __launch_bounds__(256, 1)
 loco_pair_step_fp8_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* tb,
                           const uint8_t* eb, int n_pairs, uint64_t salt) {
   ES_LOCO_PAIR_CARVE();
   loco_pair_step_body(sh, la, P, tb, ebp, bp, bm, salt, bufAp, bufAm, bufBp, bufBm,
-                      partial, rawsP, rawsM, abufP, abufM, partA);
+                      partial, rawsP, rawsM, abufP, abufM);
 }
 
 // Whole-episode (or k-step chunk) pair rollout in ONE launch: each block
@@ -951,19 +837,36 @@ loco_pair_episode_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* t
   for (int t = 1; t <= n_steps; ++t)
     loco_pair_step_body<uint16_t, false>(sh, la, P, tb, ebp, bp, bm, (uint64_t)(salt_base + t),
                         bufAp, bufAm, bufBp, bufBm, partial, rawsP, rawsM, abufP,
-                        abufM, partA);
+                        abufM);
 }
 
 // (A 128-thread 2-waves/SIMD variant — zero spills, 4 blocks/CU — was
 // measured 24% SLOWER than per-step launches and cannot match them bitwise
 // (different PART split changes summation order); removed after the A/B.)
 
-static int loco_prepare(MlpShape* sh, LocoArgs* la, const int32_t* dims_host, int32_t ndims,
-                        int64_t row_stride, float ob_clip, int32_t sdim, int32_t adim,
-                        int32_t goal_flag, int32_t terminate, int32_t noiseless_from,
-                        int32_t bins, int32_t eps, int32_t act_mode, float leak,
-                        float ctrl, float alive_bonus, float fall_thr, float dt,
-                        unsigned* lds) {
+// ---- host side --------------------------------------------------------------
+// Every entry point is loco_setup (validate, build the kernel arguments) and
+// then its group's launcher. Arguments are bound by position in
+// ops/__init__.py; loco_setup takes the ones all entry points share, in the
+// order they appear there.
+struct LocoLaunch {
+  MlpShape sh;
+  LocoArgs la;
+  LocoPtrs P;
+};
+
+static int loco_setup(LocoLaunch* L, const void* weights, const void* obmean,
+                      const void* obstd, const int32_t* dims_host, int32_t ndims,
+                      const void* seed_dev, float ob_clip, const void* ac_std_dev,
+                      int64_t row_stride, void* s_glob, void* pos, const void* goal,
+                      const void* Am, const void* Bm, const void* b0, const void* wv,
+                      const void* wa, const void* wy, const void* wh, void* alive,
+                      void* rew_total, void* member_steps, void* behv, void* mo_sum,
+                      void* mo_sumsq, int32_t sdim, int32_t adim, int32_t goal_flag,
+                      int32_t terminate, int32_t noiseless_from, int32_t bins,
+                      int32_t eps, int32_t act_mode, float leak, float ctrl,
+                      float alive_bonus, float fall_thr, float dt) {
+  MlpShape* sh = &L->sh;
   int rc = mlp_shape_init(sh, dims_host, ndims, row_stride);
   if (rc) return rc;
   if (adim > 64 || sdim > ES_MAXDIM) return -103;
@@ -973,6 +876,7 @@ static int loco_prepare(MlpShape* sh, LocoArgs* la, const int32_t* dims_host, in
   else if (act_mode == 2) out_dim = adim + 1;
   else if (act_mode == 3) out_dim = adim * 2;
   if (sh->dims[sh->n_layers] != out_dim) return -105;
+  LocoArgs* la = &L->la;
   la->S = sdim; la->A = adim; la->D = sh->dims[0]; la->goal = goal_flag;
   la->terminate = terminate; la->noiseless_from = noiseless_from; la->bins = bins;
   la->act_mode = act_mode;
@@ -980,27 +884,71 @@ static int loco_prepare(MlpShape* sh, LocoArgs* la, const int32_t* dims_host, in
   la->wrow0 = 0;
   la->leak = leak; la->ctrl = ctrl; la->alive_bonus = alive_bonus; la->fall_thr = fall_thr;
   la->dt = dt; la->ob_clip = ob_clip; la->row_stride = row_stride;
-  *lds = (unsigned)(mlp_lds_bytes(sh->maxdim) + (((sdim + 3) & ~3) + 64 + 8) * 4);
+  LocoPtrs* P = &L->P;
+  P->weights = (const uint16_t*)weights;
+  P->obmean = (const float*)obmean; P->obstd = (const float*)obstd;
+  P->ac_std_dev = (const float*)ac_std_dev; P->seed_dev = (const uint64_t*)seed_dev;
+  P->s_glob = (float*)s_glob; P->pos = (float*)pos; P->goal = (const float*)goal;
+  P->Am = (const uint16_t*)Am; P->Bm = (const float*)Bm; P->b0 = (const float*)b0;
+  P->wv = (const float*)wv; P->wa = (const float*)wa; P->wy = (const float*)wy;
+  P->wh = (const float*)wh; P->alive = (float*)alive; P->rew_total = (float*)rew_total;
+  P->member_steps = (float*)member_steps; P->behv = (float*)behv;
+  P->mo_sum = (float*)mo_sum; P->mo_sumsq = (float*)mo_sumsq;
   return 0;
 }
 
-static LocoPtrs loco_ptrs(const void* weights, const void* obmean, const void* obstd,
-                          const void* ac_std_dev, const void* seed_dev, void* s_glob,
-                          void* pos, const void* goal, const void* Am, const void* Bm,
-                          const void* b0, const void* wv, const void* wa, const void* wy,
-                          const void* wh, void* alive, void* rew_total, void* member_steps,
-                          void* behv, void* mo_sum, void* mo_sumsq) {
-  LocoPtrs P;
-  P.weights = (const uint16_t*)weights;
-  P.obmean = (const float*)obmean; P.obstd = (const float*)obstd;
-  P.ac_std_dev = (const float*)ac_std_dev; P.seed_dev = (const uint64_t*)seed_dev;
-  P.s_glob = (float*)s_glob; P.pos = (float*)pos; P.goal = (const float*)goal;
-  P.Am = (const uint16_t*)Am; P.Bm = (const float*)Bm; P.b0 = (const float*)b0;
-  P.wv = (const float*)wv; P.wa = (const float*)wa; P.wy = (const float*)wy;
-  P.wh = (const float*)wh; P.alive = (float*)alive; P.rew_total = (float*)rew_total;
-  P.member_steps = (float*)member_steps; P.behv = (float*)behv;
-  P.mo_sum = (float*)mo_sum; P.mo_sumsq = (float*)mo_sumsq;
-  return P;
+// dynamic LDS of the one-member kernels at 256 threads
+static unsigned loco_lds_bytes(const LocoLaunch& L) {
+  return (unsigned)(mlp_lds_bytes(L.sh.maxdim) + (((L.la.S + 3) & ~3) + 64 + 8) * 4);
+}
+
+// es_loco_step / es_loco_step_f32: WT = uint16_t (bf16 blob) or float
+template <typename WT>
+static int loco_launch_step(LocoLaunch& L, int32_t n_pop, uint64_t salt, void* stream) {
+  constexpr bool f32 = sizeof(WT) == 4;
+  if (f32) mlp_shape_vec_f32(&L.sh, L.la.row_stride);
+  auto* kern = f32 ? loco_step_f32_kernel : loco_step_kernel;
+  kern<<<dim3((unsigned)n_pop), dim3(256), loco_lds_bytes(L), (hipStream_t)stream>>>(
+      L.sh, L.la, L.P, salt);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// es_loco_episode / es_loco_episode_f32
+template <typename WT>
+static int loco_launch_episode(LocoLaunch& L, int32_t n_steps, int32_t member_base,
+                               int32_t n_members, int32_t salt_base, int32_t wrow0,
+                               int32_t block_threads, void* stream) {
+  constexpr bool f32 = sizeof(WT) == 4;
+  if (f32) mlp_shape_vec_f32(&L.sh, L.la.row_stride);
+  L.la.wrow0 = wrow0;
+  const bool wide = block_threads == 512;
+  auto* kern = wide ? (f32 ? loco_episode512_f32_kernel : loco_episode512_kernel)
+                    : (f32 ? loco_episode_f32_kernel : loco_episode_kernel);
+  // partial[] grows with the block size
+  const unsigned lds = loco_lds_bytes(L) + (wide ? 256 * 8 * 4 : 0);
+  kern<<<dim3((unsigned)n_members), dim3(wide ? 512 : 256), lds, (hipStream_t)stream>>>(
+      L.sh, L.la, L.P, member_base, n_steps, salt_base);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
+// The three pair entry points: `kern` is the step kernel (tail = salt), its
+// fp8 sibling or the episode kernel (tail = n_steps, salt_base); EB is the
+// element type of its eps rows. Grid = n_pairs * eps blocks, each evaluating
+// the +/- slots of one (pair, episode).
+template <typename EB, typename... Tail>
+static int loco_launch_pair(void (*kern)(MlpShape, LocoArgs, LocoPtrs, const uint16_t*,
+                                         const EB*, int, Tail...),
+                            const LocoLaunch& L, const void* theta_row,
+                            const void* eps_rows, int32_t n_pairs, void* stream,
+                            Tail... tail) {
+  const unsigned lds = (unsigned)mlp_pair_lds_bytes(L.sh.maxdim, L.la.S);
+  const unsigned grid = (unsigned)(n_pairs * L.la.eps);
+  kern<<<dim3(grid), dim3(256), lds, (hipStream_t)stream>>>(
+      L.sh, L.la, L.P, (const uint16_t*)theta_row, (const EB*)eps_rows, n_pairs, tail...);
+  ES_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int es_loco_step(const void* weights, const void* obmean, const void* obstd,
@@ -1015,20 +963,13 @@ extern "C" int es_loco_step(const void* weights, const void* obmean, const void*
                             int32_t terminate, int32_t noiseless_from, int32_t bins,
                             int32_t eps, int32_t act_mode, float leak, float ctrl,
                             float alive_bonus, float fall_thr, float dt, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds);
-  if (rc) return rc;
-  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
-                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
-                         mo_sum, mo_sumsq);
-  loco_step_kernel<<<dim3((unsigned)n_pop), dim3(256), lds, (hipStream_t)stream>>>(
-      sh, la, P, salt);
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, weights, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc : loco_launch_step<uint16_t>(L, n_pop, salt, stream);
 }
 
 // Split-dynamics step: forward kernel (grid = pop) then shared-A dynamics
@@ -1046,33 +987,29 @@ extern "C" int es_loco_step_split(
     int32_t noiseless_from, int32_t bins, int32_t eps, int32_t act_mode, float leak,
     float ctrl, float alive_bonus, float fall_thr, float dt, void* act_glob, int32_t G,
     void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds);
+  LocoLaunch L;
+  int rc = loco_setup(&L, weights, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
   if (rc) return rc;
   if (sdim % 8 != 0) return -106;
-  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
-                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
-                         mo_sum, mo_sumsq);
   hipStream_t s = (hipStream_t)stream;
-  loco_fwd_kernel<<<dim3((unsigned)n_pop), dim3(256), lds, s>>>(sh, la, P, salt,
-                                                                (float*)act_glob);
+  loco_fwd_kernel<<<dim3((unsigned)n_pop), dim3(256), loco_lds_bytes(L), s>>>(
+      L.sh, L.la, L.P, salt, (float*)act_glob);
   ES_CHECK_LAUNCH();
   switch (G) {
-    case 2: return loco_launch_dyn<2>(la, P, (const float*)act_glob, n_pop, s);
-    case 4: return loco_launch_dyn<4>(la, P, (const float*)act_glob, n_pop, s);
-    case 5: return loco_launch_dyn<5>(la, P, (const float*)act_glob, n_pop, s);
-    case 8: return loco_launch_dyn<8>(la, P, (const float*)act_glob, n_pop, s);
+    case 2: return loco_launch_dyn<2>(L.la, L.P, (const float*)act_glob, n_pop, s);
+    case 4: return loco_launch_dyn<4>(L.la, L.P, (const float*)act_glob, n_pop, s);
+    case 5: return loco_launch_dyn<5>(L.la, L.P, (const float*)act_glob, n_pop, s);
+    case 8: return loco_launch_dyn<8>(L.la, L.P, (const float*)act_glob, n_pop, s);
     default: return -107;
   }
 }
 
 // Antithetic-pair step: theta_row = (1, row_stride) bf16(theta);
-// eps_rows = (n_pairs, row_stride) bf16(sigma*eps). Grid = n_pairs * eps
-// blocks, each evaluating the +/- slots of one (pair, episode).
+// eps_rows = (n_pairs, row_stride) bf16(sigma*eps).
 extern "C" int es_loco_pair_step(
     const void* theta_row, const void* eps_rows, const void* obmean,
     const void* obstd, const int32_t* dims_host, int32_t ndims, const void* seed_dev,
@@ -1084,25 +1021,15 @@ extern "C" int es_loco_pair_step(
     int32_t terminate, int32_t noiseless_from, int32_t bins, int32_t eps,
     int32_t act_mode, float leak, float ctrl, float alive_bonus, float fall_thr,
     float dt, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds_unused;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds_unused);
-  if (rc) return rc;
-  LocoPtrs P = loco_ptrs(nullptr, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos,
-                         goal, Am, Bm, b0, wv, wa, wy, wh, alive, rew_total,
-                         member_steps, behv, mo_sum, mo_sumsq);
-  const int Spad = (sdim + 3) & ~3;
-  const unsigned lds =
-      (unsigned)((4 * sh.maxdim + 2 * 256 * 8 + 2 * Spad + 2 * 64 +
-                  (ES_DYN_EARLY ? 2 * 2048 : 0)) * sizeof(float));
-  const unsigned grid = (unsigned)(n_pairs * la.eps);
-  loco_pair_step_kernel<<<dim3(grid), dim3(256), lds, (hipStream_t)stream>>>(
-      sh, la, P, (const uint16_t*)theta_row, (const uint16_t*)eps_rows, n_pairs, salt);
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, nullptr, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc
+            : loco_launch_pair(loco_pair_step_kernel, L, theta_row, eps_rows, n_pairs,
+                               stream, salt);
 }
 
 // fp8-eps pair step: eps_rows = (n_pairs, row_stride) BYTES, written by
@@ -1118,25 +1045,15 @@ extern "C" int es_loco_pair_step_fp8(
     int32_t terminate, int32_t noiseless_from, int32_t bins, int32_t eps,
     int32_t act_mode, float leak, float ctrl, float alive_bonus, float fall_thr,
     float dt, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds_unused;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds_unused);
-  if (rc) return rc;
-  LocoPtrs P = loco_ptrs(nullptr, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos,
-                         goal, Am, Bm, b0, wv, wa, wy, wh, alive, rew_total,
-                         member_steps, behv, mo_sum, mo_sumsq);
-  const int Spad = (sdim + 3) & ~3;
-  const unsigned lds =
-      (unsigned)((4 * sh.maxdim + 2 * 256 * 8 + 2 * Spad + 2 * 64 +
-                  (ES_DYN_EARLY ? 2 * 2048 : 0)) * sizeof(float));
-  const unsigned grid = (unsigned)(n_pairs * la.eps);
-  loco_pair_step_fp8_kernel<<<dim3(grid), dim3(256), lds, (hipStream_t)stream>>>(
-      sh, la, P, (const uint16_t*)theta_row, (const uint8_t*)eps_rows, n_pairs, salt);
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, nullptr, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc
+            : loco_launch_pair(loco_pair_step_fp8_kernel, L, theta_row, eps_rows,
+                               n_pairs, stream, salt);
 }
 
 // Pair-episode: n_steps consecutive env steps per launch (n_steps =
@@ -1153,26 +1070,15 @@ extern "C" int es_loco_pair_episode(
     int32_t terminate, int32_t noiseless_from, int32_t bins, int32_t eps,
     int32_t act_mode, float leak, float ctrl, float alive_bonus, float fall_thr,
     float dt, int32_t n_steps, int32_t salt_base, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds_unused;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds_unused);
-  if (rc) return rc;
-  LocoPtrs P = loco_ptrs(nullptr, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos,
-                         goal, Am, Bm, b0, wv, wa, wy, wh, alive, rew_total,
-                         member_steps, behv, mo_sum, mo_sumsq);
-  const int Spad = (sdim + 3) & ~3;
-  const unsigned lds =
-      (unsigned)((4 * sh.maxdim + 2 * 256 * 8 + 2 * Spad + 2 * 64 +
-                  (ES_DYN_EARLY ? 2 * 2048 : 0)) * sizeof(float));
-  const unsigned grid = (unsigned)(n_pairs * la.eps);
-  loco_pair_episode_kernel<<<dim3(grid), dim3(256), lds, (hipStream_t)stream>>>(
-      sh, la, P, (const uint16_t*)theta_row, (const uint16_t*)eps_rows, n_pairs,
-      n_steps, salt_base);
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, nullptr, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc
+            : loco_launch_pair(loco_pair_episode_kernel, L, theta_row, eps_rows, n_pairs,
+                               stream, n_steps, salt_base);
 }
 
 extern "C" int es_loco_episode(const void* weights, const void* obmean, const void* obstd,
@@ -1190,29 +1096,15 @@ extern "C" int es_loco_episode(const void* weights, const void* obmean, const vo
                                int32_t bins, int32_t eps, int32_t act_mode, float leak,
                                float ctrl, float alive_bonus, float fall_thr, float dt,
                                int32_t block_threads, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds);
-  if (rc) return rc;
-  la.wrow0 = wrow0;
-  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
-                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
-                         mo_sum, mo_sumsq);
-  if (block_threads == 512) {
-    const unsigned lds512 = lds + 256 * 8 * 4;  // partial[] grows with nth
-    loco_episode512_kernel<<<dim3((unsigned)n_members), dim3(512), lds512,
-                             (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
-                                                    salt_base);
-  } else {
-    loco_episode_kernel<<<dim3((unsigned)n_members), dim3(256), lds,
-                          (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
-                                                 salt_base);
-  }
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, weights, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc
+            : loco_launch_episode<uint16_t>(L, n_steps, member_base, n_members, salt_base,
+                                            wrow0, block_threads, stream);
 }
 
 // fp32-weights step / episode: the argument lists of es_loco_step and
@@ -1228,21 +1120,13 @@ extern "C" int es_loco_step_f32(
     int32_t sdim, int32_t adim, int32_t goal_flag, int32_t terminate,
     int32_t noiseless_from, int32_t bins, int32_t eps, int32_t act_mode, float leak,
     float ctrl, float alive_bonus, float fall_thr, float dt, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds);
-  if (rc) return rc;
-  mlp_shape_vec_f32(&sh, row_stride);
-  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
-                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
-                         mo_sum, mo_sumsq);
-  loco_step_f32_kernel<<<dim3((unsigned)n_pop), dim3(256), lds, (hipStream_t)stream>>>(
-      sh, la, P, salt);
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, weights, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc : loco_launch_step<float>(L, n_pop, salt, stream);
 }
 
 extern "C" int es_loco_episode_f32(
@@ -1256,28 +1140,13 @@ extern "C" int es_loco_episode_f32(
     int32_t goal_flag, int32_t terminate, int32_t noiseless_from, int32_t bins,
     int32_t eps, int32_t act_mode, float leak, float ctrl, float alive_bonus,
     float fall_thr, float dt, int32_t block_threads, void* stream) {
-  MlpShape sh;
-  LocoArgs la;
-  unsigned lds;
-  int rc = loco_prepare(&sh, &la, dims_host, ndims, row_stride, ob_clip, sdim, adim,
-                        goal_flag, terminate, noiseless_from, bins, eps, act_mode, leak,
-                        ctrl, alive_bonus, fall_thr, dt, &lds);
-  if (rc) return rc;
-  mlp_shape_vec_f32(&sh, row_stride);
-  la.wrow0 = wrow0;
-  LocoPtrs P = loco_ptrs(weights, obmean, obstd, ac_std_dev, seed_dev, s_glob, pos, goal,
-                         Am, Bm, b0, wv, wa, wy, wh, alive, rew_total, member_steps, behv,
-                         mo_sum, mo_sumsq);
-  if (block_threads == 512) {
-    const unsigned lds512 = lds + 256 * 8 * 4;  // partial[] grows with nth
-    loco_episode512_f32_kernel<<<dim3((unsigned)n_members), dim3(512), lds512,
-                                 (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
-                                                        salt_base);
-  } else {
-    loco_episode_f32_kernel<<<dim3((unsigned)n_members), dim3(256), lds,
-                              (hipStream_t)stream>>>(sh, la, P, member_base, n_steps,
-                                                     salt_base);
-  }
-  ES_CHECK_LAUNCH();
-  return 0;
+  LocoLaunch L;
+  int rc = loco_setup(&L, weights, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  return rc ? rc
+            : loco_launch_episode<float>(L, n_steps, member_base, n_members, salt_base,
+                                         wrow0, block_threads, stream);
 }

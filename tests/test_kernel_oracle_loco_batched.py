@@ -26,7 +26,7 @@ together. Head cases, all with a 17-wide head (PART = 15) unless stated:
                                           + drain<7>
 
 Action term: A = 1, 9 (drain only), 16 (one full batch), 17 (batch + 1),
-64 (four batches, the most loco_prepare allows).
+64 (four batches, the most loco_setup allows).
 
 Pair epilogue: S=256 (one output per thread), S=376 (second sweep on 120
 threads), S=8 (part of wave 0 holds outputs, the minus member's bookkeeping

@@ -1,4 +1,4 @@
-"""Stream loops of the pair rollout kernels (ES_STREAM_PIPE) against the
+"""Stream loops of the pair rollout kernels (the set rings) against the
 float64 oracle: the set ring of the pair A stream (loco_dyn_partials_pair,
 rollout_loco.hip) and of the fp8 pair forward's vec layers
 (mlp_layers_pair_fp8, mlp_core.h).
@@ -66,9 +66,10 @@ two 2-pair sub-trips run, and rem = n - 4 T - 2 pairs (0..4) drain:
   hidden, O = I = 256   8     16       3   2      flagship hidden layer
                                                    (16 actions x 16 bins)
 
-All 63 cases pass on MI355X with the ring on (default) and on the parent's
-loops (``ES_STREAM_PIPE=0``); ``build()`` + ``oracle()`` of every case run on
-the CPU.
+All 63 cases pass on MI355X with the rings; that they also pass on the
+copy-rotated loops the rings replaced was established at commit b3e3cdb,
+which still carried those loops behind a preprocessor switch (since
+removed). ``build()`` + ``oracle()`` of every case run on the CPU.
 """
 import numpy as np
 import pytest

@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Cross-compile kernel-variant libraries for same-box A/B sweeps.
+"""Cross-compile control kernel libraries for same-box A/B runs.
 
-Builds one _hip_ops .so per (ES_DEPTH_E, ES_DEPTH_T) pair-forward ring
-configuration into es_pytorch_amd/ops/variants/ (gitignored; DOES travel
-with the gpurun snapshot). On the GPU box:
+Builds one _hip_ops .so from the kernel sources of each given git revision
+(checked out into a temp tree) into es_pytorch_amd/ops/variants/
+(gitignored), e.g. the parent commit as the control arm of alternated runs:
 
-    ES_HIP_SO=es_pytorch_amd/ops/variants/hip_e8t4.so \
+    python tools/build_variants.py --revs HEAD~1
+
+Then, on the GPU box, alternate the tree's own library with the control:
+
+    python tools/kbench.py --pair --graph --steps 1000
+    ES_HIP_SO=es_pytorch_amd/ops/variants/hip_HEADp1.so \
         python tools/kbench.py --pair --graph --steps 1000
-
-Optionally also builds a control .so from a given git revision's kernel
-sources (checked out into a temp tree):
-
-    python tools/build_variants.py --revs HEAD~1 --depths 4,4 8,4
 """
 import argparse
 import os
@@ -24,18 +24,6 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from es_pytorch_amd import ops  # noqa: E402
 
 VAR_DIR = os.path.join(os.path.dirname(ops.__file__), "variants")
-
-
-def build_depth_variant(de: int, dt: int, minwaves: int = 0) -> str:
-    os.makedirs(VAR_DIR, exist_ok=True)
-    name = f"hip_e{de}t{dt}" + (f"w{minwaves}" if minwaves else "") + ".so"
-    out = os.path.join(VAR_DIR, name)
-    flags = [f"-DES_DEPTH_E={de}", f"-DES_DEPTH_T={dt}"]
-    if minwaves:
-        flags.append(f"-DES_PAIR_MINWAVES={minwaves}")
-    ops.build_hip(force=True, extra_flags=flags, out=out)
-    print("built", out, flags)
-    return out
 
 
 def build_rev_control(rev: str) -> str:
@@ -62,13 +50,8 @@ def build_rev_control(rev: str) -> str:
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--depths", nargs="*", default=["4,4", "8,4"],
-                    help="DE,DT[,minwaves] combos")
-    ap.add_argument("--revs", nargs="*", default=[],
+    ap.add_argument("--revs", nargs="+", required=True,
                     help="git revisions to build as control arms")
     a = ap.parse_args()
-    for spec in a.depths:
-        parts = [int(x) for x in spec.split(",")]
-        build_depth_variant(*parts)
     for rev in a.revs:
         build_rev_control(rev)

@@ -12,7 +12,7 @@ innermost ones, and the own blocks of loops that hold others) prints
     are in flight when a wait retires which of them.
 
     python tools/isa_loops.py es_pytorch_amd/ops/csrc/hip/rollout_loco.hip \
-        loco_pair_step_fp8_kernel [--min-len 40] [-D ES_STREAM_PIPE=0]
+        loco_pair_step_fp8_kernel [--min-len 40] [-D NAME=VALUE]
 
 It is a reading aid: it reports ordinary opcodes and checks nothing.
 """
@@ -146,7 +146,7 @@ def main():
                     help="hide loops shorter than this many instructions")
     ap.add_argument("--top", type=int, default=16, help="histogram rows")
     ap.add_argument("-D", dest="defs", action="append", default=[],
-                    help="preprocessor definition, e.g. -D ES_STREAM_PIPE=0")
+                    help="preprocessor definition passed to hipcc, e.g. -D NDEBUG=1")
     ap.add_argument("--has", default="",
                     help="only loops holding an opcode with this prefix")
     ap.add_argument("--asm", help="read this assembly file instead of compiling")
