@@ -58,7 +58,8 @@ ES_HD float u01_open(uint32_t u) {
   return ((float)u + 1.0f) * 2.3283064365386963e-10f;
 }
 
-// uniform in [0, 1)
+// uniform in [0, 1]: (float)u rounds up to 2^32 for the top 128 inputs
+// (u >= 2^32 - 128), so 1.0f is reached; harmless for cos/sin(2*pi*u)
 ES_HD float u01(uint32_t u) {
   return (float)u * 2.3283064365386963e-10f;
 }

@@ -4,7 +4,9 @@ Plain numpy, float64 maths, no torch ops and no code shared with
 ``es_pytorch_amd``: every formula below is written out from the documented
 semantics (``envs/locomotion.py``, ``GpuEngine._step_body``, the layout notes
 at the top of ``pheno.hip``), so a bug in the kernels' shared device code
-cannot hide in both arms of a comparison.
+cannot hide in both arms of a comparison. The random numbers are restated
+too: Philox4x32-10 is written out from the paper and checked against its
+published known-answer vectors (tests/test_oracle64_noise_cpu.py).
 
 Every maths function takes a ``dtype``. ``float64`` is the oracle;
 ``float32`` re-runs the SAME natural-order evaluation in single precision and
@@ -128,6 +130,87 @@ def fp8_byte_position(dims):
     return pos
 
 
+# ---------------------------------------------------------------------- noise
+_U32 = np.uint64(0xFFFFFFFF)
+_SH32 = np.uint64(32)
+PHILOX_M = (np.uint64(0xD2511F53), np.uint64(0xCD9E8D57))     # round multipliers
+PHILOX_W = (np.uint64(0x9E3779B9), np.uint64(0xBB67AE85))     # key bumps
+NOISE_TAG = 0x6573616D                                        # counter word 3
+ACTION_STREAM = 0xAC
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32 with 10 rounds (Salmon et al., SC'11; Random123), written
+    out from the paper: counter = 4 words, key = 2 words, each a scalar or an
+    array of 32-bit values (they broadcast). Returns the 4 output words as
+    uint64 arrays holding 32-bit values."""
+    c0, c1, c2, c3 = (np.asarray(w, dtype=np.uint64) & _U32 for w in counter)
+    k0, k1 = (np.asarray(w, dtype=np.uint64) & _U32 for w in key)
+    for _ in range(10):
+        p0 = PHILOX_M[0] * c0            # 32 x 32 -> 64 bits, no overflow
+        p1 = PHILOX_M[1] * c2
+        c0, c1, c2, c3 = ((p1 >> _SH32) ^ c1 ^ k0, p1 & _U32,
+                          (p0 >> _SH32) ^ c3 ^ k1, p0 & _U32)
+        k0 = (k0 + PHILOX_W[0]) & _U32
+        k1 = (k1 + PHILOX_W[1]) & _U32
+    return c0, c1, c2, c3
+
+
+def normal4(g, seed, stream, dtype=np.float64):
+    """The four standard normals of group(s) `g` under (seed, stream).
+
+    Counter (g lo, g hi, stream, NOISE_TAG), key (seed lo, seed hi). The
+    uniforms are float32 values and their roundings are part of the contract:
+    u1, u3 = (float32(word) + 1) * 2^-32 in (0, 1] from words 0 and 2,
+    u2, u4 = float32(word) * 2^-32 in [0, 1] from words 1 and 3 (the top 128
+    words round up to 2^32, so 1.0 is reached). Box-Muller in `dtype` with the
+    float32 value of 2*pi: (r1 cos, r1 sin, r2 cos, r2 sin), r = sqrt(-2 log u).
+    Returns an array of shape g.shape + (4,)."""
+    g = np.asarray(g, dtype=np.uint64)
+    seed = int(seed) & (2 ** 64 - 1)
+    w = philox4x32_10((g & _U32, g >> _SH32, int(stream) & 0xFFFFFFFF, NOISE_TAG),
+                      (seed & 0xFFFFFFFF, seed >> 32))
+    w = [np.broadcast_to(x, g.shape).astype(np.float32) for x in w]   # one rounding
+    scale = np.float32(2.0 ** -32)
+    one = np.float32(1.0)
+    u1, u3 = (w[0] + one) * scale, (w[2] + one) * scale
+    u2, u4 = w[1] * scale, w[3] * scale
+    two_pi = dtype(np.float32(6.2831853071795864769))
+    r1 = np.sqrt(dtype(-2.0) * np.log(u1.astype(dtype)))
+    r2 = np.sqrt(dtype(-2.0) * np.log(u3.astype(dtype)))
+    t1 = two_pi * u2.astype(dtype)
+    t2 = two_pi * u4.astype(dtype)
+    return np.stack([r1 * np.cos(t1), r1 * np.sin(t1), r2 * np.cos(t2), r2 * np.sin(t2)],
+                    axis=-1)
+
+
+def noise_table(n, seed, stream, dtype=np.float64):
+    """Noise table of n elements: element i is component i & 3 of group i >> 2."""
+    groups = np.arange((int(n) + 3) // 4, dtype=np.uint64)
+    return normal4(groups, seed, stream, dtype).reshape(-1)[:int(n)]
+
+
+def action_noise(seed, ctr, dtype=np.float64):
+    """Action-noise draw(s) at counter(s) `ctr`: component 0 of the group
+    `ctr` of stream ACTION_STREAM."""
+    return normal4(ctr, seed, ACTION_STREAM, dtype)[..., 0]
+
+
+def action_draws(seed, members, width, cols, dtype=np.float64):
+    """z[k, d] = action_noise(seed, members[k] * width + d) for d < cols: the
+    draws of absolute slots `members` of a net whose output is `width` wide."""
+    ctr = np.asarray(members, dtype=np.uint64)[:, None] * np.uint64(width) + \
+        np.arange(cols, dtype=np.uint64)[None, :]
+    return action_noise(seed, ctr, dtype)
+
+
+def noise_seed(noise):
+    """Key of a launch: seed_dev + salt in 64-bit arithmetic, or the salt
+    alone when there is no seed_dev (seed None)."""
+    base = 0 if noise["seed"] is None else int(noise["seed"])
+    return (base + int(noise["salt"])) & (2 ** 64 - 1)
+
+
 # -------------------------------------------------------------------- forward
 def _act(v, dtype):
     return np.tanh(v.astype(dtype, copy=False))
@@ -161,14 +244,21 @@ def mlp_forward(dims, weight_row, x, act_final=1, dtype=np.float64):
 
 def policy_actions(dims, weight_rows, obs, obmean, obstd, ob_clip, members=None,
                    eps=1, wrow0=0, act_final=1, act_mode=0, bins=0, alow=None,
-                   arange=None, loco=False, dtype=np.float64):
+                   arange=None, loco=False, dtype=np.float64, noise=None):
     """Actions of evaluation slots `members` (default: every row of obs).
 
     obs[k] is the observation of slot members[k]; slot b uses weight row
     b // eps - wrow0. Decode: act_mode 2 -> outputs 1.. (output 0 is the std),
     act_mode 3 -> first half, bins > 1 -> per-dim argmax over `bins` logits
     mapped to alow + arange * j/(bins-1) (or to [-1, 1] when loco=True), else
-    the raw outputs. Action noise is not modelled (noise off).
+    the raw outputs.
+
+    noise: None (noise off) or a dict of seed (None: no seed_dev), salt,
+    ac_std and noiseless_from. Slots b < noiseless_from get
+    z = action_noise(seed + salt, b * odim + d), odim the net's output width:
+    the raw decode adds ac_std * z iff ac_std != 0, mode 2 adds out[0] * z and
+    mode 3 |out[adim + d]| * z iff that std != 0, whatever ac_std is; the
+    binned decode never draws. The actions are returned unclamped.
     Returns (actions, net_outputs).
     """
     obs = np.asarray(obs)
@@ -181,10 +271,19 @@ def policy_actions(dims, weight_rows, obs, obmean, obstd, ob_clip, members=None,
         np.asarray(obstd).astype(dtype)
     xn = np.minimum(np.maximum(xn, -clip), clip)
     out = mlp_forward(dims, w, xn, act_final, dtype)
-    if act_mode == 2:
-        return out[:, 1:].copy(), out
-    if act_mode == 3:
-        return out[:, :out.shape[1] // 2].copy(), out
+    odim = out.shape[1]
+    noisy = None
+    if noise is not None:
+        noisy = (members < int(noise["noiseless_from"]))[:, None]
+    if act_mode in (2, 3):
+        if act_mode == 2:
+            a, std = out[:, 1:].copy(), out[:, :1]
+        else:
+            a, std = out[:, :odim // 2].copy(), np.abs(out[:, odim // 2:2 * (odim // 2)])
+        if noisy is not None and noisy.any():
+            z = action_draws(noise_seed(noise), members, odim, a.shape[1], dtype)
+            a = np.where(noisy & (std != 0), a + std * z, a)
+        return a, out
     if bins and bins > 1:
         adim = out.shape[1] // bins
         best = out.reshape(nb, adim, bins).argmax(axis=2).astype(dtype)
@@ -192,7 +291,13 @@ def policy_actions(dims, weight_rows, obs, obmean, obstd, ob_clip, members=None,
         if loco:
             return dtype(-1.0) + dtype(2.0) * frac, out
         return np.asarray(alow).astype(dtype) + np.asarray(arange).astype(dtype) * frac, out
-    return out.copy(), out
+    a = out.copy()
+    if noisy is not None and noisy.any():
+        ac_std = dtype(np.float32(noise["ac_std"]))
+        if ac_std != 0:
+            z = action_draws(noise_seed(noise), members, odim, odim, dtype)
+            a = np.where(noisy, a + ac_std * z, a)
+    return a, out
 
 
 def top2_logit_gap(net_out, bins):
@@ -220,7 +325,8 @@ def loco_obs(state, goal_flag, dtype=np.float64):
     return np.concatenate([s, rel], axis=1)
 
 
-def loco_step(state, env, policy, members=None, dtype=np.float64):
+def loco_step(state, env, policy, members=None, dtype=np.float64, noise=None,
+              salt_base=0):
     """One env step for evaluation slots `members` (default all).
 
     state: dict of (B, ...) arrays — s (B,S), pos (B,3), goal (B,2) or None,
@@ -228,8 +334,12 @@ def loco_step(state, env, policy, members=None, dtype=np.float64):
     env: dict — A (S,S) VALUES of the bf16 matrix, B (Adim,S), b0, wv, wy, wh
     (S,), wa (Adim,), leak, ctrl, alive_bonus, fall_thr, dt, terminate, goal.
     policy: kwargs of policy_actions except obs/members/loco/dtype.
+    noise: None or a dict of seed, ac_std and noiseless_from (see
+    policy_actions); the step draws with salt salt_base + 1, so salt_base =
+    s - 1 reproduces a per-step launch with salt s.
     Returns (new_state, info); rows outside `members` are returned unchanged.
-    info holds h, actions and net outputs of the stepped slots.
+    info holds h, the clamped actions, the actions before the clamp and the
+    net outputs of the stepped slots.
     """
     f = lambda v: dtype(np.float32(v))
     B = state["s"].shape[0]
@@ -240,7 +350,10 @@ def loco_step(state, env, policy, members=None, dtype=np.float64):
     S = sub["s"].shape[1]
 
     obs = loco_obs(sub, g, dtype)
-    act, net = policy_actions(obs=obs, members=members, loco=True, dtype=dtype, **policy)
+    if noise is not None:
+        noise = dict(noise, salt=int(salt_base) + 1)
+    act, net = policy_actions(obs=obs, members=members, loco=True, dtype=dtype,
+                              noise=noise, **policy)
     a = np.minimum(np.maximum(act, dtype(-1.0)), dtype(1.0))
 
     A = np.asarray(env["A"]).astype(dtype)
@@ -300,16 +413,18 @@ def loco_step(state, env, policy, members=None, dtype=np.float64):
         if new[k] is not None:
             out[k] = out[k].copy()
             out[k][members] = new[k]
-    info = {"h": h.astype(np.float64), "actions": a, "net_out": net, "done": done,
-            "alive_before": live}
+    info = {"h": h.astype(np.float64), "actions": a, "act_raw": act, "net_out": net,
+            "done": done, "alive_before": live}
     return out, info
 
 
-def loco_rollout(state, env, policy, n_steps, members=None, dtype=np.float64):
-    """n_steps consecutive loco_step calls; returns (state, [info per step])."""
+def loco_rollout(state, env, policy, n_steps, members=None, dtype=np.float64,
+                 noise=None, salt_base=0):
+    """n_steps consecutive loco_step calls, step t = 1.. drawing with salt
+    salt_base + t; returns (state, [info per step])."""
     infos = []
-    for _ in range(n_steps):
-        state, info = loco_step(state, env, policy, members, dtype)
+    for t in range(n_steps):
+        state, info = loco_step(state, env, policy, members, dtype, noise, salt_base + t)
         infos.append(info)
     return state, infos
 

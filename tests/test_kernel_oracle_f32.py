@@ -396,11 +396,15 @@ ENV_SCALARS = dict(leak=0.35, ctrl=0.05, alive_bonus=1.0, fall_thr=0.0, dt=0.07)
 
 
 def C(kernel, S, hidden, seed=0, adim=3, goal=0, terminate=1, bins=0, act_mode=0,
-      members=6, eps=1, n_steps=1, block=256, member_base=0, wrow0=0):
+      members=6, eps=1, n_steps=1, block=256, member_base=0, wrow0=0, ac_std=0.0,
+      seed_dev=None, salt=1, salt_base=0, noiseless_from=0):
+    """ac_std, seed_dev, salt / salt_base and noiseless_from: the noise of
+    tests/test_kernel_oracle_noise.py; the defaults are noise off."""
     return dict(kernel=kernel, S=S, hidden=hidden, seed=seed, adim=adim, goal=goal,
                 terminate=terminate, bins=bins, act_mode=act_mode, members=members,
                 eps=eps, n_steps=n_steps, block=block, member_base=member_base,
-                wrow0=wrow0)
+                wrow0=wrow0, ac_std=ac_std, seed_dev=seed_dev, salt=salt,
+                salt_base=salt_base, noiseless_from=noiseless_from)
 
 
 LOCO_CASES = {
@@ -432,11 +436,11 @@ def case_dims(c):
     return [c["S"] + 2 * c["goal"], c["hidden"], out]
 
 
-def build_loco(name):
+def build_loco(name, cases=None):
     """Numpy inputs of a case: env matrices, a prescribed initial state with
     non-zero accumulators and mixed alive, the fp32 weight blob and the
     oracle's policy/env dicts. No GPU work."""
-    c = LOCO_CASES[name]
+    c = (LOCO_CASES if cases is None else cases)[name]
     rng = np.random.RandomState(2000 + sum(ord(ch) for ch in name) + 7919 * c["seed"])
     S, A, g = c["S"], c["adim"], c["goal"]
     dims = case_dims(c)
@@ -474,14 +478,18 @@ def build_loco(name):
                 nslots=nslots)
 
 
-def loco_oracle(case):
+def loco_oracle(case, with_infos=False):
     """(y64 state, E32 per buffer over the stepped slots); asserts that no
     discrete outcome sits on a rounding edge and both outcomes occur."""
     c, m = case["c"], case["members"]
     env = {k: v for k, v in case["env"].items() if k != "A_bits"}
+    noise = dict(seed=c["seed_dev"], ac_std=c["ac_std"],
+                 noiseless_from=c["noiseless_from"])
+    salt_base = c["salt_base"] if c["kernel"] == "episode" else c["salt"] - 1
     y64, infos = loco_rollout(case["state"], env, case["policy"], c["n_steps"], m,
-                              np.float64)
-    y32, _ = loco_rollout(case["state"], env, case["policy"], c["n_steps"], m, np.float32)
+                              np.float64, noise, salt_base)
+    y32, _ = loco_rollout(case["state"], env, case["policy"], c["n_steps"], m, np.float32,
+                          noise, salt_base)
     e32 = {k: err_scale(y32[k][m], y64[k][m]) for k in STATE_KEYS}
     for info in infos:
         assert (np.abs(info["h"] - np.float32(env["fall_thr"])) > 1e-3).all(), \
@@ -494,6 +502,8 @@ def loco_oracle(case):
         now = y64["alive"][m] > 0
         assert (was & ~now).any() and (was & now).any(), \
             "need both terminated and surviving members"
+    if with_infos:
+        return y64, e32, infos
     return y64, e32
 
 
@@ -506,7 +516,8 @@ def launch_loco(dev, case):
     A_d = torch.from_numpy(np.ascontiguousarray(env["A_bits"]).view(np.int16).copy()) \
         .view(torch.bfloat16).to(dev)
     mean_d, std_d, w = _t(case["obmean"], dev), _t(case["obstd"], dev), _t(case["w"], dev)
-    acstd = torch.zeros(1, dtype=torch.float32, device=dev)
+    acstd = torch.full((1,), c["ac_std"], dtype=torch.float32, device=dev)
+    seed_d = None if c["seed_dev"] is None else _t(np.array([c["seed_dev"]], np.int64), dev)
     dims_arr = np.array(case["dims"], dtype=np.int32)
     goal_ptr = st["goal"].data_ptr() if c["goal"] else None
     bufs = (st["s"].data_ptr(), st["pos"].data_ptr(), goal_ptr, A_d.data_ptr(),
@@ -515,19 +526,21 @@ def launch_loco(dev, case):
             st["alive"].data_ptr(), st["rew_total"].data_ptr(),
             st["member_steps"].data_ptr(), st["behv"].data_ptr(),
             st["mo_sum"].data_ptr(), st["mo_sumsq"].data_ptr())
-    flags = (c["S"], c["adim"], c["goal"], c["terminate"], 0, c["bins"], c["eps"],
-             c["act_mode"])
+    flags = (c["S"], c["adim"], c["goal"], c["terminate"], c["noiseless_from"], c["bins"],
+             c["eps"], c["act_mode"])
     scal = tuple(float(env[k]) for k in ("leak", "ctrl", "alive_bonus", "fall_thr", "dt"))
-    head = (mean_d.data_ptr(), std_d.data_ptr(), dims_arr.ctypes.data, len(dims_arr), None)
+    head = (mean_d.data_ptr(), std_d.data_ptr(), dims_arr.ctypes.data, len(dims_arr),
+            None if seed_d is None else seed_d.data_ptr())
     tail = (OB_CLIP, acstd.data_ptr(), case["stride"])
     if c["kernel"] == "step":
         assert c["n_steps"] == 1
-        rc = lib.es_loco_step_f32(w.data_ptr(), *head, 1, *tail, *bufs, case["nslots"],
+        rc = lib.es_loco_step_f32(w.data_ptr(), *head, c["salt"], *tail, *bufs, case["nslots"],
                                   *flags, *scal, _stream(dev))
     else:
         mb = c["member_base"]
         rc = lib.es_loco_episode_f32(w.data_ptr(), *head, c["n_steps"], *tail, *bufs, mb,
-                                     case["nslots"] - mb, 0, c["wrow0"], *flags, *scal,
+                                     case["nslots"] - mb, c["salt_base"], c["wrow0"], *flags,
+                                     *scal,
                                      c["block"], _stream(dev))
     assert rc == 0, rc
     torch.cuda.synchronize(dev)

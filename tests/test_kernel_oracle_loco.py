@@ -5,7 +5,8 @@ Every launch shape runs on test-owned buffers (dynamics matrices included, so
 the state dim S is free) and every output buffer is compared:
 continuous ones by ``|kernel - oracle64| <= 16 * E32`` (E32: the same step in
 numpy float32), ``member_steps``/``alive`` and everything a dead member owns
-exactly. Accumulators start non-zero and ``alive`` is mixed, ``ac_std`` is 0.
+exactly. Accumulators start non-zero and ``alive`` is mixed, ``ac_std`` is 0
+(tests/test_kernel_oracle_noise.py runs the same helpers with noise on).
 
 State dims (dynamics A-matvec, 256 threads: OCT = S/8, PART = 256 // OCT):
   S=8 OCT=1 | S=64 tail loop only | S=144 8-deep prologue + guarded drain, no
@@ -81,11 +82,16 @@ ENV_SCALARS = dict(leak=0.35, ctrl=0.05, alive_bonus=1.0, fall_thr=0.0, dt=0.07)
 
 
 def C(kernel, S, hidden, seed=0, adim=3, goal=0, terminate=1, bins=0, act_mode=0,
-      members=6, eps=1, sigma=0.02, n_steps=1, G=0, block=256, member_base=0, wrow0=0):
+      members=6, eps=1, sigma=0.02, n_steps=1, G=0, block=256, member_base=0, wrow0=0,
+      ac_std=0.0, seed_dev=None, salt=1, salt_base=0, noiseless_from=0):
+    """Noise (tests/test_kernel_oracle_noise.py): ac_std, seed_dev (None: a
+    null pointer), noiseless_from, and `salt` for the per-step entry points or
+    `salt_base` for the episode ones. The defaults are noise off."""
     return dict(kernel=kernel, S=S, hidden=hidden, seed=seed, adim=adim, goal=goal,
                 terminate=terminate, bins=bins, act_mode=act_mode, members=members,
                 eps=eps, sigma=sigma, n_steps=n_steps, G=G, block=block,
-                member_base=member_base, wrow0=wrow0)
+                member_base=member_base, wrow0=wrow0, ac_std=ac_std, seed_dev=seed_dev,
+                salt=salt, salt_base=salt_base, noiseless_from=noiseless_from)
 
 
 # `members` counts evaluation slots (step/split/episode) or pairs (pair kernels)
@@ -185,10 +191,10 @@ def _bf16_blob(rng, dims, rows, scale=None):
     return bits, bf16_bits_to_f64(bits)[:, :n], stride
 
 
-def build(name):
+def build(name, cases=CASES):
     """Numpy inputs of a case: env matrices, initial state, weight blobs and
     the oracle's policy/env dicts. No GPU work."""
-    c = CASES[name]
+    c = cases[name]
     rng = np.random.RandomState(1000 + sum(ord(ch) for ch in name) + 7919 * c["seed"])
     S, A, g = c["S"], c["adim"], c["goal"]
     dims = case_dims(c)
@@ -255,14 +261,27 @@ def build(name):
                 nslots=nslots)
 
 
-def oracle(case):
+EPISODE_KERNELS = ("episode", "pair_episode")
+
+
+def case_noise(c):
+    """(noise dict, salt_base) the oracle gets for a case: step t of an
+    episode kernel draws with salt_base + t, a per-step launch with `salt`."""
+    noise = dict(seed=c["seed_dev"], ac_std=c["ac_std"],
+                 noiseless_from=c["noiseless_from"])
+    return noise, c["salt_base"] if c["kernel"] in EPISODE_KERNELS else c["salt"] - 1
+
+
+def oracle(case, with_infos=False):
     """(y64 state, E32 per buffer over the stepped slots); asserts that no
     discrete outcome sits on a rounding edge."""
     c, m = case["c"], case["members"]
     env = {k: v for k, v in case["env"].items() if k != "A_bits"}
+    noise, salt_base = case_noise(c)
     y64, infos = loco_rollout(case["state"], env, case["policy"], c["n_steps"], m,
-                              np.float64)
-    y32, _ = loco_rollout(case["state"], env, case["policy"], c["n_steps"], m, np.float32)
+                              np.float64, noise, salt_base)
+    y32, _ = loco_rollout(case["state"], env, case["policy"], c["n_steps"], m, np.float32,
+                          noise, salt_base)
     e32 = {k: err_scale(y32[k][m], y64[k][m]) for k in STATE_KEYS}
     for info in infos:
         assert (np.abs(info["h"] - np.float32(env["fall_thr"])) > 1e-3).all(), \
@@ -274,6 +293,8 @@ def oracle(case):
         now = y64["alive"][m] > 0
         assert (was & ~now).any() and (was & now).any(), \
             "need both terminated and surviving members"
+    if with_infos:
+        return y64, e32, infos
     return y64, e32
 
 
@@ -293,7 +314,8 @@ def launch(dev, case):
     ev = {k: t(env[k]) for k in ("B", "b0", "wv", "wa", "wy", "wh")}
     A_d = bf16_tensor(env["A_bits"], dev)
     mean_d, std_d = t(case["obmean"]), t(case["obstd"])
-    acstd = torch.zeros(1, dtype=torch.float32, device=dev)
+    acstd = torch.full((1,), c["ac_std"], dtype=torch.float32, device=dev)
+    seed_d = None if c["seed_dev"] is None else t(np.array([c["seed_dev"]], np.int64))
     dims_arr = np.array(case["dims"], dtype=np.int32)
     goal_ptr = st["goal"].data_ptr() if c["goal"] else None
     bufs = (st["s"].data_ptr(), st["pos"].data_ptr(), goal_ptr, A_d.data_ptr(),
@@ -302,16 +324,18 @@ def launch(dev, case):
             st["alive"].data_ptr(), st["rew_total"].data_ptr(),
             st["member_steps"].data_ptr(), st["behv"].data_ptr(),
             st["mo_sum"].data_ptr(), st["mo_sumsq"].data_ptr())
-    flags = (c["S"], c["adim"], c["goal"], c["terminate"], 0, c["bins"], c["eps"],
-             c["act_mode"])
+    flags = (c["S"], c["adim"], c["goal"], c["terminate"], c["noiseless_from"], c["bins"],
+             c["eps"], c["act_mode"])
     scal = tuple(float(env[k]) for k in ("leak", "ctrl", "alive_bonus", "fall_thr", "dt"))
-    head = (mean_d.data_ptr(), std_d.data_ptr(), dims_arr.ctypes.data, len(dims_arr), None)
+    head = (mean_d.data_ptr(), std_d.data_ptr(), dims_arr.ctypes.data, len(dims_arr),
+            None if seed_d is None else seed_d.data_ptr())
     tail = (OB_CLIP, acstd.data_ptr(), case["stride"])
     k = c["kernel"]
     keep = []
     if k in ("step", "split"):
         w = bf16_tensor(case["blobs"]["weights"], dev)
-        args = (w.data_ptr(),) + head + (1,) + tail + bufs + (case["nslots"],) + flags + scal
+        args = (w.data_ptr(),) + head + (c["salt"],) + tail + bufs + (case["nslots"],) + \
+            flags + scal
         if k == "step":
             rc = lib.es_loco_step(*args, _stream(dev))
         else:
@@ -325,18 +349,18 @@ def launch(dev, case):
         pre = (th.data_ptr(), ep.data_ptr()) + head
         post = bufs + (c["members"],) + flags + scal
         if k == "pair_episode":
-            rc = lib.es_loco_pair_episode(*pre, *tail, *post, c["n_steps"], 0,
+            rc = lib.es_loco_pair_episode(*pre, *tail, *post, c["n_steps"], c["salt_base"],
                                           _stream(dev))
         else:
             fn = lib.es_loco_pair_step_fp8 if k == "fp8" else lib.es_loco_pair_step
             assert c["n_steps"] == 1
-            rc = fn(*pre, 1, *tail, *post, _stream(dev))
+            rc = fn(*pre, c["salt"], *tail, *post, _stream(dev))
     else:
         w = bf16_tensor(case["blobs"]["weights"], dev)
         mb = c["member_base"]
         rc = lib.es_loco_episode(w.data_ptr(), *head, c["n_steps"], *tail, *bufs, mb,
-                                 case["nslots"] - mb, 0, c["wrow0"], *flags, *scal,
-                                 c["block"], _stream(dev))
+                                 case["nslots"] - mb, c["salt_base"], c["wrow0"], *flags,
+                                 *scal, c["block"], _stream(dev))
     assert rc == 0, rc
     torch.cuda.synchronize(dev)
     out = {kk: st[kk].cpu().numpy() for kk in STATE_KEYS}
@@ -415,12 +439,10 @@ def _bits(tensor):
     return tensor.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
 
 
-@pytest.mark.parametrize("mode", ["step", "split", "pair", "fp8", "episode",
-                                  "pair_episode", "noiseless", "noiseless_pair"])
-def test_engine_wiring_one_step(dev, mode):
-    """The engine's own launch wrappers, one step on a registry env: pins the
-    40-argument call order that the direct calls above bypass. Every env
-    scalar is distinct so a swapped pair of arguments shows."""
+def wiring_setup(dev, mode, ac_std=0.0, seed_dev=None):
+    """An engine of `mode` on a registry env with a prescribed state in its
+    own buffers; the oracle's inputs are read back from those buffers.
+    Returns (eng, state, tensors, members, policy, envd)."""
     eng = _engine(dev, mode)
     env = eng.env
     env.dt, env.ctrl_cost, env.leak, env.alive_bonus = 0.07, 0.05, 0.35, 1.0
@@ -428,7 +450,9 @@ def test_engine_wiring_one_step(dev, mode):
     B, S, D, n = eng.B, env.sdim, env.ob_dim, eng.n
     f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
     eng._upload_offsets()
-    eng.acstd_dev.fill_(0.0)
+    eng.acstd_dev.fill_(ac_std)
+    if seed_dev is not None:
+        eng.seed_dev.copy_(torch.tensor([seed_dev], dtype=torch.int64))
     eng._pheno()
     alive = (np.arange(B) % 3 != 1).astype(np.float32)
     state = dict(s=f32(rng.randn(B, S) * 0.6), pos=f32(rng.randn(B, 3)), goal=None,
@@ -464,20 +488,50 @@ def test_engine_wiring_one_step(dev, mode):
                 wy=env.wy.cpu().numpy(), wh=env.wh.cpu().numpy(), leak=env.leak,
                 ctrl=env.ctrl_cost, alive_bonus=env.alive_bonus, dt=env.dt, terminate=1,
                 goal=0, fall_thr=0.0)
-    # fall threshold: centre of the widest gap in the oracle's h over the live
-    # stepped slots, so both outcomes occur and none sits on a rounding edge
-    _, infos = loco_rollout(state, envd, policy, 1, members, np.float64)
+    return eng, state, tensors, members, policy, envd
+
+
+def wiring_reference(eng, state, policy, envd, members, n_steps=1, noise=None,
+                     salt_base=0):
+    """Sets the fall threshold (engine env and envd) and returns (y64, E32).
+
+    Threshold: centre of the widest gap in the oracle's first-step h over the
+    live stepped slots, so both outcomes occur, that keeps every h of every
+    step more than 1e-3 away (h does not depend on the threshold)."""
+    roll = lambda dt: loco_rollout(state, envd, policy, n_steps, members, dt, noise,
+                                   salt_base)
+    _, infos = roll(np.float64)
     hs = np.sort(infos[0]["h"][state["alive"][members] > 0])
+    all_h = np.concatenate([info["h"] for info in infos])
     if hs.size > 1:
-        j = int(np.argmax(np.diff(hs)))
-        thr = 0.5 * (hs[j] + hs[j + 1])
+        mids = 0.5 * (hs[:-1] + hs[1:])
+        order = np.argsort(-np.diff(hs), kind="stable")
+        thr = next(float(np.float32(mids[j])) for j in order
+                   if (np.abs(all_h - np.float32(mids[j])) > 1e-3).all())
     else:
-        thr = hs[0] + 0.25      # one live slot (noiseless member): it falls
-    env.fall_threshold = envd["fall_thr"] = float(np.float32(thr))
-    y64, infos = loco_rollout(state, envd, policy, 1, members, np.float64)
-    y32, _ = loco_rollout(state, envd, policy, 1, members, np.float32)
-    assert (np.abs(infos[0]["h"] - envd["fall_thr"]) > 1e-3).all()
+        thr = float(np.float32(hs[0] + 0.25))   # one live slot (noiseless member): it falls
+    eng.env.fall_threshold = envd["fall_thr"] = thr
+    y64, infos = roll(np.float64)
+    y32, _ = roll(np.float32)
+    for info in infos:
+        assert (np.abs(info["h"] - envd["fall_thr"]) > 1e-3).all()
     e32 = {k: err_scale(y32[k][members], y64[k][members]) for k in STATE_KEYS}
+    return y64, e32
+
+
+def wiring_state(tensors):
+    return {k: tt.cpu().numpy() for k, tt in tensors.items()}
+
+
+@pytest.mark.parametrize("mode", ["step", "split", "pair", "fp8", "episode",
+                                  "pair_episode", "noiseless", "noiseless_pair"])
+def test_engine_wiring_one_step(dev, mode):
+    """The engine's own launch wrappers, one step on a registry env: pins the
+    40-argument call order that the direct calls above bypass. Every env
+    scalar is distinct so a swapped pair of arguments shows."""
+    eng, state, tensors, members, policy, envd = wiring_setup(dev, mode)
+    mm = (eng.M - 1) * eng.eps
+    y64, e32 = wiring_reference(eng, state, policy, envd, members)
 
     if mode in ("step", "split", "pair", "fp8"):
         eng._loco_step(0)
@@ -488,5 +542,4 @@ def test_engine_wiring_one_step(dev, mode):
     else:
         eng._loco_noiseless_episode()
     torch.cuda.synchronize(dev)
-    got = {k: tt.cpu().numpy() for k, tt in tensors.items()}
-    compare(f"wiring_{mode}", got, y64, e32, state, members)
+    compare(f"wiring_{mode}", wiring_state(tensors), y64, e32, state, members)

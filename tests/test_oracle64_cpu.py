@@ -89,8 +89,10 @@ def test_e4m3_encode_matches_torch_everywhere():
 # --------------------------------------------------------------------- layout
 def _all_fp8_dims():
     from tests.test_kernel_oracle_loco import FP8_LOCO_DIMS
+    from tests.test_kernel_oracle_noise import FP8_NOISE_DIMS
     from tests.test_kernel_oracle_ops import FP8_PHENO_DIMS
     return {**{"loco_" + k: v for k, v in FP8_LOCO_DIMS.items()},
+            **{"noise_" + k: v for k, v in FP8_NOISE_DIMS.items()},
             **{"pheno_" + k: v for k, v in FP8_PHENO_DIMS.items()}}
 
 
