@@ -53,6 +53,15 @@ from es_pytorch_amd.rollout.results import RewardResult
 from es_pytorch_amd.utils.novelty import novelty_batch
 from es_pytorch_amd.utils.rankers import CenteredRanker, Ranker
 
+# Env steps per launch that the fp8 pair path uses when the config has no
+# `steps_per_launch`: the smallest k within the spread of the best in the
+# round-6 sweep (profiles/README.md, "Round 6", k x variant table). Only
+# while every (pair, episode) block is resident at once, at the 4 blocks per
+# CU the multi-step kernel is sized for: past that the same table has every
+# k > 1 level with or behind per-step launches (pop 10240).
+FP8_PAIR_STEPS_PER_LAUNCH = 50
+FP8_PAIR_CHUNK_BLOCKS_PER_CU = 4
+
 
 def forward_perm(dims: List[int]) -> torch.Tensor:
     """Map forward-layout element index -> flat state_dict index.
@@ -122,7 +131,12 @@ class GpuEngine:
             pair_rollout = eps_fp8 = split_dyn = False
         # steps per launch in "step" mode: k>1 runs k consecutive env steps
         # per kernel launch (bounded block drift, fewer launch boundaries)
-        self.steps_per_launch = int(cfg.general.get("steps_per_launch", 1) or 1)
+        # A value in the config is honoured as given (1 = one launch per
+        # step); without one the fp8 pair path picks its own below
+        # (FP8_PAIR_STEPS_PER_LAUNCH) and every other path keeps 1.
+        spl = cfg.general.get("steps_per_launch", None)
+        self._steps_per_launch_auto = not spl
+        self.steps_per_launch = int(spl or 1)
         self.cfg = cfg
         self.comm = comm
         self.policy = policy
@@ -277,7 +291,6 @@ class GpuEngine:
         # 56.3, 1024 84.4 vs 59.1 — the halved load count pays earlier).
         fp8_possible = (bool(cfg.general.get("eps_fp8", False))
                         if eps_fp8 is None else bool(eps_fp8)) and \
-            self.rollout_mode == "step" and self.steps_per_launch == 1 and \
             self._fp8_layout_ok(self.dims)
         if pair_rollout is not None:
             want_pair = bool(pair_rollout)
@@ -296,6 +309,11 @@ class GpuEngine:
         want_fp8 = (bool(cfg.general.get("eps_fp8", False))
                     if eps_fp8 is None else bool(eps_fp8))
         self.eps_fp8 = fp8_possible and self.pair_rollout
+        if self.eps_fp8 and self._steps_per_launch_auto and d.type == "cuda":
+            slots = FP8_PAIR_CHUNK_BLOCKS_PER_CU * \
+                torch.cuda.get_device_properties(d).multi_processor_count
+            if self.pairs * self.eps <= slots:
+                self.steps_per_launch = FP8_PAIR_STEPS_PER_LAUNCH
         if want_fp8 and not self.eps_fp8 and comm.rank == 0:
             import sys
             print("[engine] eps_fp8 requested but unavailable for this "
@@ -496,7 +514,9 @@ class GpuEngine:
         launches); trajectories are bitwise-identical to per-step launches."""
         env = self.env
         goal_ptr = env.goal.data_ptr() if env.goal_conditioned else None
-        ops.check(ops.hip().es_loco_pair_episode(
+        fn, name = (ops.hip().es_loco_pair_episode_fp8, "es_loco_pair_episode_fp8") \
+            if self.eps_fp8 else (ops.hip().es_loco_pair_episode, "es_loco_pair_episode")
+        ops.check(fn(
             self.theta_row.data_ptr(), self.eps_rows.data_ptr(),
             self.obmean.data_ptr(), self.obstd.data_ptr(),
             self.dims_arr.ctypes.data, len(self.dims_arr),
@@ -516,7 +536,7 @@ class GpuEngine:
             float(env.leak), float(env.ctrl_cost), float(env.alive_bonus),
             float(env.fall_threshold), float(env.dt),
             self.max_steps if n_steps is None else int(n_steps), int(salt_base),
-            self._stream()), "es_loco_pair_episode")
+            self._stream()), name)
 
     def _loco_noiseless_episode(self):
         # 512-thread blocks: the single-member episode is latency-serial, so
@@ -598,6 +618,14 @@ class GpuEngine:
                 with torch.cuda.stream(s):
                     for t in range(3):
                         body(t)
+                    # the kernel the graph will hold, where it is not body's
+                    if self.fused and (self.rollout_mode == "episode"
+                                       or self.steps_per_launch > 1):
+                        if self.pair_rollout:
+                            self._loco_pair_episode(n_steps=2)
+                        else:
+                            mm = (self.M - 1) * self.eps
+                            self._loco_episode(0, mm, mm, n_steps=2)
                     if self.fused:
                         self._loco_noiseless_episode()  # warm the episode kernel
                 torch.cuda.current_stream(self.device).wait_stream(s)

@@ -194,6 +194,9 @@ def _bind_hip(lib):
                                          p, p, p, p, p, p,
                                          i32, i32, i32, i32, i32, i32, i32, i32, i32,
                                          f32, f32, f32, f32, f32, i32, i32, p]
+    lib.es_loco_pair_episode_fp8.argtypes = lib.es_loco_pair_episode.argtypes
+    # (blocks per CU the kernel is sized for: 3 or 4, carry the state in LDS)
+    lib.es_loco_pair_episode_fp8_config.argtypes = [i32, i32]
     lib.es_loco_episode.argtypes = [p, p, p, p, i32, p, i32, f32, p, i64,
                                     p, p, p, p, p, p, p, p, p, p,
                                     p, p, p, p, p, p,
@@ -209,7 +212,8 @@ def _bind_hip(lib):
                "es_noise_fill", "es_pheno_bf16", "es_pheno_fp8", "es_mlp_fwd",
                "es_grad_gather", "es_adam_step", "es_sgd_step", "es_loco_step",
                "es_loco_step_split", "es_loco_pair_step", "es_loco_pair_step_fp8",
-               "es_loco_pair_episode", "es_loco_episode"]:
+               "es_loco_pair_episode", "es_loco_pair_episode_fp8",
+               "es_loco_pair_episode_fp8_config", "es_loco_episode"]:
         getattr(lib, fn).restype = i32
 
 

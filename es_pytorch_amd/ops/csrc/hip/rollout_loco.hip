@@ -225,10 +225,22 @@ struct LocoBook {
 // one-member call, so NM only changes when loads issue and how often waves
 // wait. When S % 8 == 0 the A-matvec partials must already be in part[m]
 // (loco_dyn_partials*); otherwise the scalar fallback reads Am directly.
-template <int NM>
+//
+// CARRY (multi-step kernels): when `carry` is set (block-uniform; requires
+// S % 8 == 0, where raws[m][o] is read by its own thread only) the thread
+// that owns output o also leaves s' in raws[m][o] and the next step's
+// normalized observation in obs[m][o] — loco_build_obs_pair's expression,
+// division included — and member m's bookkeeping lane writes the goal dims
+// from the position it just computed. The caller's next step then skips the
+// s_glob reload and the obs pass. s_glob is still written every step.
+// Measured 0.1-0.5 us per step SLOWER than the reload at the flagship shape
+// (profiles/README.md, round 6), so es_loco_pair_episode_fp8 has it off by
+// default.
+template <int NM, bool CARRY = false>
 __device__ __forceinline__ void loco_dyn_finish_n(
     const LocoArgs& la, const LocoPtrs& P, const int* b, const float* const* raws,
-    const float* const* abuf, float* const* part, int tid, int nth) {
+    const float* const* abuf, float* const* part, int tid, int nth,
+    float* const* obs = nullptr, bool carry = false) {
   const int S = la.S, A = la.A;
   float w_alive[NM];  // pre-step alive, used as obstat weight
   float *sb[NM], *ms[NM], *mq[NM];
@@ -266,6 +278,19 @@ __device__ __forceinline__ void loco_dyn_finish_n(
       }
     }
   }
+  // carried goal dims: normalization constants load with the lane's scalars
+  float* obs_me = nullptr;
+  float gmean0 = 0.0f, gmean1 = 0.0f, gsd0 = 1.0f, gsd1 = 1.0f;
+  if constexpr (CARRY) {
+    if (carry && la.goal && book) {
+      obs_me = obs[0];
+#pragma unroll
+      for (int m = 1; m < NM; ++m)
+        if (wid == m) obs_me = obs[m];
+      gmean0 = P.obmean[S]; gmean1 = P.obmean[S + 1];
+      gsd0 = P.obstd[S]; gsd1 = P.obstd[S + 1];
+    }
+  }
 
   float p0[NM], p1[NM], p2[NM], p3[NM];
 #pragma unroll
@@ -277,6 +302,9 @@ __device__ __forceinline__ void loco_dyn_finish_n(
     for (int o = tid; o < S; o += nth) {
       // every load of this output whose address is known up front
       const float b0o = P.b0[o], wvo = P.wv[o], wyo = P.wy[o], who = P.wh[o];
+      float omean = 0.0f, osd = 1.0f;
+      if constexpr (CARRY)
+        if (carry) { omean = P.obmean[o]; osd = P.obstd[o]; }
       float mso[NM], mqo[NM];
 #pragma unroll
       for (int m = 0; m < NM; ++m)
@@ -327,6 +355,11 @@ __device__ __forceinline__ void loco_dyn_finish_n(
       for (int m = 0; m < NM; ++m) {
         const float sn = (1.0f - la.leak) * raws[m][o] + la.leak * tanhf(p[m]);
         sb[m][o] = sn;
+        if constexpr (CARRY)
+          if (carry) {
+            const_cast<float*>(raws[m])[o] = sn;
+            obs[m][o] = fclampf((sn - omean) / osd, -la.ob_clip, la.ob_clip);
+          }
         p0[m] = fmaf(sn, wvo, p0[m]);
         p1[m] = fmaf(sn, wyo, p1[m]);
         p2[m] = fmaf(sn, who, p2[m]);
@@ -411,6 +444,16 @@ __device__ __forceinline__ void loco_dyn_finish_n(
       ms_me[S + 1] = bk.ms1 + rel1;
       mq_me[S + 1] = bk.mq1 + rel1 * rel1;
     }
+    if constexpr (CARRY) {
+      // goal-relative obs dims of the next step, from the position stored
+      // above (loco_build_obs_pair's expression on the same float values)
+      if (carry && la.goal) {
+        const float rel0 = (bk.gx - px) * 0.1f;
+        const float rel1 = (bk.gy - py) * 0.1f;
+        obs_me[S] = fclampf((rel0 - gmean0) / gsd0, -la.ob_clip, la.ob_clip);
+        obs_me[S + 1] = fclampf((rel1 - gmean1) / gsd1, -la.ob_clip, la.ob_clip);
+      }
+    }
   }
   // next step of an episode kernel: alive/pos written above are read by
   // other threads, and raws/part are rewritten
@@ -428,15 +471,18 @@ __device__ __forceinline__ void loco_dyn_finish(
 }
 
 // One fused epilogue for both members of a pair.
+template <bool CARRY = false>
 __device__ __forceinline__ void loco_dyn_finish_pair(
     const LocoArgs& la, const LocoPtrs& P, int bp, int bm, const float* rawsP,
     const float* rawsM, const float* abufP, const float* abufM, float* partP,
-    float* partM, int tid, int nth) {
+    float* partM, int tid, int nth, float* obsP = nullptr, float* obsM = nullptr,
+    bool carry = false) {
   const int bs[2] = {bp, bm};
   const float* const rs[2] = {rawsP, rawsM};
   const float* const as[2] = {abufP, abufM};
   float* const ps[2] = {partP, partM};
-  loco_dyn_finish_n<2>(la, P, bs, rs, as, ps, tid, nth);
+  float* const os[2] = {obsP, obsM};
+  loco_dyn_finish_n<2, CARRY>(la, P, bs, rs, as, ps, tid, nth, os, carry);
 }
 
 template <typename WT = uint16_t>
@@ -754,16 +800,23 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
   __syncthreads();
 }
 
-// EB = uint16_t (bf16 eps rows) or uint8_t (fp8 row-pair-interleaved rows)
-template <typename EB, bool PIPE = true>
+// EB = uint16_t (bf16 eps rows) or uint8_t (fp8 row-pair-interleaved rows).
+// tid is the caller's threadIdx.x (the multi-step fp8 kernel hands in a copy
+// the optimizer cannot see through). CARRY: `have` = the previous step of
+// this launch left raws and the normalized obs in LDS, `keep` = this step
+// leaves them for the next (loco_dyn_finish_n); both block-uniform.
+template <typename EB, bool PIPE = true, bool CARRY = false>
 __device__ __forceinline__ void loco_pair_step_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P,
     const uint16_t* tb, const EB* eb, int bp, int bm, uint64_t salt,
     float* bufAp, float* bufAm, float* bufBp, float* bufBm, float* partial,
-    float* rawsP, float* rawsM, float* abufP, float* abufM) {
-  const int tid = threadIdx.x, nth = blockDim.x;
-  loco_build_obs_pair(la, P, bp, bm, bufAp, bufAm, rawsP, rawsM, tid, nth);
-  __syncthreads();
+    float* rawsP, float* rawsM, float* abufP, float* abufM, int tid,
+    bool have = false, bool keep = false) {
+  const int nth = blockDim.x;
+  if (!(CARRY && have)) {
+    loco_build_obs_pair(la, P, bp, bm, bufAp, bufAm, rawsP, rawsM, tid, nth);
+    __syncthreads();
+  }
   float *ap, *am;
   if constexpr (sizeof(EB) == 1)
     mlp_layers_pair_fp8(tb, (const uint8_t*)eb, sh, bufAp, bufAm, bufBp, bufBm,
@@ -777,8 +830,8 @@ __device__ __forceinline__ void loco_pair_step_body(
   if (la.S % 8 == 0)
     loco_dyn_partials_pair<PIPE>(P.Am, la.S, rawsP, rawsM, partial, partial + 2048,
                                  tid, nth);
-  loco_dyn_finish_pair(la, P, bp, bm, rawsP, rawsM, abufP, abufM, partial,
-                       partial + 2048, tid, nth);
+  loco_dyn_finish_pair<CARRY>(la, P, bp, bm, rawsP, rawsM, abufP, abufM, partial,
+                              partial + 2048, tid, nth, bufAp, bufAm, keep);
 }
 
 #define ES_LOCO_PAIR_CARVE()                                     \
@@ -803,7 +856,7 @@ loco_pair_step_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* tb,
                       const uint16_t* eb, int n_pairs, uint64_t salt) {
   ES_LOCO_PAIR_CARVE();
   loco_pair_step_body(sh, la, P, tb, ebp, bp, bm, salt, bufAp, bufAm, bufBp, bufBm,
-                      partial, rawsP, rawsM, abufP, abufM);
+                      partial, rawsP, rawsM, abufP, abufM, threadIdx.x);
 }
 
 __global__ void __launch_bounds__(256, 1)
@@ -811,7 +864,7 @@ loco_pair_step_fp8_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* 
                           const uint8_t* eb, int n_pairs, uint64_t salt) {
   ES_LOCO_PAIR_CARVE();
   loco_pair_step_body(sh, la, P, tb, ebp, bp, bm, salt, bufAp, bufAm, bufBp, bufBm,
-                      partial, rawsP, rawsM, abufP, abufM);
+                      partial, rawsP, rawsM, abufP, abufM, threadIdx.x);
 }
 
 // Whole-episode (or k-step chunk) pair rollout in ONE launch: each block
@@ -837,7 +890,52 @@ loco_pair_episode_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* t
   for (int t = 1; t <= n_steps; ++t)
     loco_pair_step_body<uint16_t, false>(sh, la, P, tb, ebp, bp, bm, (uint64_t)(salt_base + t),
                         bufAp, bufAm, bufBp, bufBm, partial, rawsP, rawsM, abufP,
-                        abufM);
+                        abufM, threadIdx.x);
+}
+
+// The fp8 sibling: the set-ring body (PIPE = true) in a step loop. Left to
+// itself the optimizer hoists every per-lane address and every load that does
+// not change from step to step out of the loop and holds them across it
+// (naive loop under a 4-wave bound: 64 VGPRs spilled, 292 B/lane scratch).
+// So once per step the kernel passes its loop-invariant inputs — every
+// pointer, the slot indices and the thread index — through an empty asm the
+// optimizer cannot see through: a few scalar moves per step, and the body
+// compiles as it does in the per-step kernel. MINB = blocks per CU the
+// register budget is sized for (4: 128 VGPRs, 3: 134-135); none of the four
+// instantiations spills or uses scratch. CARRY keeps the state and the next
+// observation in LDS between the steps of a launch (loco_dyn_finish_n); it
+// falls back to the reload when S % 8 != 0.
+#define ES_OPAQUE_S(x) asm volatile("" : "+s"(x))
+#define ES_OPAQUE_V(x) asm volatile("" : "+v"(x))
+template <int MINB, bool CARRY>
+__global__ void __launch_bounds__(256, MINB)
+loco_pair_chunk_fp8_kernel(MlpShape sh, LocoArgs la, LocoPtrs Pk, const uint16_t* tb,
+                           const uint8_t* eb, int n_pairs, int n_steps, int salt_base) {
+  ES_LOCO_PAIR_CARVE();
+  LocoPtrs P = Pk;
+  int bpl = bp, bml = bm;
+  int tid = threadIdx.x;
+  const bool oct8 = (la.S % 8 == 0);
+#pragma clang loop unroll(disable)
+  for (int t = 1; t <= n_steps; ++t) {
+    ES_OPAQUE_S(P.weights); ES_OPAQUE_S(P.obmean); ES_OPAQUE_S(P.obstd);
+    ES_OPAQUE_S(P.ac_std_dev); ES_OPAQUE_S(P.seed_dev); ES_OPAQUE_S(P.s_glob);
+    ES_OPAQUE_S(P.pos); ES_OPAQUE_S(P.goal); ES_OPAQUE_S(P.Bm); ES_OPAQUE_S(P.b0);
+    ES_OPAQUE_S(P.wv); ES_OPAQUE_S(P.wa); ES_OPAQUE_S(P.wy); ES_OPAQUE_S(P.wh);
+    ES_OPAQUE_S(P.Am); ES_OPAQUE_S(P.alive); ES_OPAQUE_S(P.rew_total);
+    ES_OPAQUE_S(P.member_steps); ES_OPAQUE_S(P.behv); ES_OPAQUE_S(P.mo_sum);
+    ES_OPAQUE_S(P.mo_sumsq);
+    ES_OPAQUE_S(tb); ES_OPAQUE_S(ebp); ES_OPAQUE_S(bpl); ES_OPAQUE_S(bml);
+    ES_OPAQUE_V(tid);
+    // 1 - leak and -ob_clip are otherwise computed once and held in VGPRs
+    // (the last 4 spilled registers of the 4-block variant). Laundering the
+    // LDS pointers or the integer members of `la` as well brings spills back.
+    ES_OPAQUE_S(la.leak); ES_OPAQUE_S(la.ob_clip);
+    loco_pair_step_body<uint8_t, true, CARRY>(
+        sh, la, P, tb, ebp, bpl, bml, (uint64_t)(salt_base + t), bufAp, bufAm, bufBp,
+        bufBm, partial, rawsP, rawsM, abufP, abufM, tid, oct8 && t > 1,
+        oct8 && t < n_steps);
+  }
 }
 
 // (A 128-thread 2-waves/SIMD variant — zero spills, 4 blocks/CU — was
@@ -1079,6 +1177,58 @@ extern "C" int es_loco_pair_episode(
   return rc ? rc
             : loco_launch_pair(loco_pair_episode_kernel, L, theta_row, eps_rows, n_pairs,
                                stream, n_steps, salt_base);
+}
+
+// Which loco_pair_chunk_fp8_kernel instantiation es_loco_pair_episode_fp8
+// launches: blocks per CU the register budget is sized for (3 or 4) and
+// whether the state is carried in LDS between the steps of a launch. A
+// process-wide switch so that tools/kbench.py can A/B the four variants; the
+// defaults are the round-6 sweep's choice (profiles/README.md).
+#define ES_CHUNK_FP8_MIN_BLOCKS 4
+#define ES_CHUNK_FP8_CARRY 0
+static int g_chunk_fp8_min_blocks = ES_CHUNK_FP8_MIN_BLOCKS;
+static int g_chunk_fp8_carry = ES_CHUNK_FP8_CARRY;
+
+// min_blocks = 0 restores the defaults.
+extern "C" int es_loco_pair_episode_fp8_config(int32_t min_blocks, int32_t carry) {
+  if (min_blocks == 0) {
+    min_blocks = ES_CHUNK_FP8_MIN_BLOCKS;
+    carry = ES_CHUNK_FP8_CARRY;
+  }
+  if (min_blocks != 3 && min_blocks != 4) return -108;
+  g_chunk_fp8_min_blocks = min_blocks;
+  g_chunk_fp8_carry = carry != 0;
+  return 0;
+}
+
+// fp8-eps pair-episode: the argument list of es_loco_pair_episode; eps_rows
+// as for es_loco_pair_step_fp8. Step i of the launch draws its action noise
+// with salt_base + i, i = 1..n_steps.
+extern "C" int es_loco_pair_episode_fp8(
+    const void* theta_row, const void* eps_rows, const void* obmean,
+    const void* obstd, const int32_t* dims_host, int32_t ndims, const void* seed_dev,
+    float ob_clip, const void* ac_std_dev, int64_t row_stride,
+    void* s_glob, void* pos, const void* goal, const void* Am, const void* Bm,
+    const void* b0, const void* wv, const void* wa, const void* wy, const void* wh,
+    void* alive, void* rew_total, void* member_steps, void* behv, void* mo_sum,
+    void* mo_sumsq, int32_t n_pairs, int32_t sdim, int32_t adim, int32_t goal_flag,
+    int32_t terminate, int32_t noiseless_from, int32_t bins, int32_t eps,
+    int32_t act_mode, float leak, float ctrl, float alive_bonus, float fall_thr,
+    float dt, int32_t n_steps, int32_t salt_base, void* stream) {
+  LocoLaunch L;
+  int rc = loco_setup(&L, nullptr, obmean, obstd, dims_host, ndims, seed_dev, ob_clip,
+                      ac_std_dev, row_stride, s_glob, pos, goal, Am, Bm, b0, wv, wa, wy,
+                      wh, alive, rew_total, member_steps, behv, mo_sum, mo_sumsq, sdim,
+                      adim, goal_flag, terminate, noiseless_from, bins, eps, act_mode,
+                      leak, ctrl, alive_bonus, fall_thr, dt);
+  if (rc) return rc;
+  const bool four = g_chunk_fp8_min_blocks == 4, carry = g_chunk_fp8_carry != 0;
+  auto* kern = four ? (carry ? loco_pair_chunk_fp8_kernel<4, true>
+                             : loco_pair_chunk_fp8_kernel<4, false>)
+                    : (carry ? loco_pair_chunk_fp8_kernel<3, true>
+                             : loco_pair_chunk_fp8_kernel<3, false>);
+  return loco_launch_pair(kern, L, theta_row, eps_rows, n_pairs, stream, n_steps,
+                          salt_base);
 }
 
 extern "C" int es_loco_episode(const void* weights, const void* obmean, const void* obstd,

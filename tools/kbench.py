@@ -34,6 +34,10 @@ def main():
     p.add_argument("--fp8", action="store_true", help="fp8 sigma*eps stream")
     p.add_argument("--fp32", action="store_true",
                    help="fp32 member rows + fp32-weight forward (weights_dtype=fp32)")
+    p.add_argument("--chunk-blocks", type=int, default=None, choices=[3, 4],
+                   help="fp8 multi-step kernel: blocks per CU it is sized for")
+    p.add_argument("--chunk-carry", type=int, default=None, choices=[0, 1],
+                   help="fp8 multi-step kernel: keep the state in LDS between steps")
     args = p.parse_args()
 
     from es_pytorch_amd.config import AttrDict
@@ -46,6 +50,12 @@ def main():
     from es_pytorch_amd.parallel.comm import Comm
     from es_pytorch_amd.utils.rankers import CenteredRanker
 
+    if args.chunk_blocks is not None or args.chunk_carry is not None:
+        from es_pytorch_amd import ops
+        ops.check(ops.hip().es_loco_pair_episode_fp8_config(
+            3 if args.chunk_blocks is None else args.chunk_blocks,
+            1 if args.chunk_carry is None else args.chunk_carry),
+            "es_loco_pair_episode_fp8_config")
     dev = torch.device("cuda", 0)
     comm = Comm(dev)
     torch.manual_seed(0)
