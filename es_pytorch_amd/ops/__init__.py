@@ -197,6 +197,16 @@ def _bind_hip(lib):
     lib.es_loco_pair_episode_fp8.argtypes = lib.es_loco_pair_episode.argtypes
     # (blocks per CU the kernel is sized for: 3 or 4, carry the state in LDS)
     lib.es_loco_pair_episode_fp8_config.argtypes = [i32, i32]
+    # (level of launch invariants staged in LDS: -1 automatic, 0/1/2 forced)
+    # (absent from a library of an earlier revision loaded through ES_HIP_SO)
+    if hasattr(lib, "es_loco_pair_episode_fp8_stage"):
+        lib.es_loco_pair_episode_fp8_stage.argtypes = [i32]
+        lib.es_loco_pair_episode_fp8_stage.restype = i32
+        # (highest level the automatic choice may take)
+        lib.es_loco_pair_episode_fp8_stage_max.argtypes = [i32]
+        lib.es_loco_pair_episode_fp8_stage_max.restype = i32
+        lib.es_loco_pair_episode_fp8_last_stage.argtypes = []
+        lib.es_loco_pair_episode_fp8_last_stage.restype = i32
     lib.es_loco_episode.argtypes = [p, p, p, p, i32, p, i32, f32, p, i64,
                                     p, p, p, p, p, p, p, p, p, p,
                                     p, p, p, p, p, p,

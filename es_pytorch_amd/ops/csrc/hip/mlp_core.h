@@ -444,17 +444,86 @@ __device__ __forceinline__ void bf8e_fma_pair_pk(es_u32x4 t, uint32_t elo, uint3
   }
 }
 
+// The scalar layer of mlp_layers_pair_fp8 on weights staged in LDS (Tl bf16
+// theta, El fp8 eps, element-ordered): its two arms, PART > 1 and PART == 1,
+// statement for statement. A copy and not a shared lambda or template: every
+// form of sharing tried moved the register allocation of the per-step kernel,
+// whose assembly a staged level must leave alone; and the pointer's address
+// space has to be fixed at compile time (a run-time choice between LDS and
+// global gives a generic pointer and flat loads).
+template <typename BIAS>
+__device__ __forceinline__ void mlp_pair_fp8_scalar_staged(
+    const uint16_t* Tl, const uint8_t* El, int I, int O, const float* xp,
+    const float* xm, float* yp, float* ym, float* partial, float* partm, int tid,
+    int nthreads, bool do_act, BIAS bias_pm) {
+  const int PART = nthreads / O;
+  if (PART > 1) {
+    const int oi = tid % O, ip = tid / O;
+    float accp = 0.0f, accm = 0.0f;
+    if (ip < PART) {
+      es_walk_batched<EsTE8>(
+          ip, PART, I, [&](int r) { return EsTE8{Tl[r * O + oi], El[r * O + oi]}; },
+          [&](EsTE8 w, int r) {
+            const float tw = bf2f(w.t), ew = fp8_byte(w.e);
+            accp = fmaf(tw + ew, xp[r], accp);
+            accm = fmaf(tw - ew, xm[r], accm);
+          });
+      partial[ip * O + oi] = accp;
+      partm[ip * O + oi] = accm;
+    }
+    __syncthreads();
+    for (int o = tid; o < O; o += nthreads) {
+      float sp, sm;
+      bias_pm(o, sp, sm);
+      for (int p = 0; p < PART; ++p) {
+        sp += partial[p * O + o];
+        sm += partm[p * O + o];
+      }
+      yp[o] = do_act ? tanhf(sp) : sp;
+      ym[o] = do_act ? tanhf(sm) : sm;
+    }
+  } else {
+    for (int o = tid; o < O; o += nthreads) {
+      float accp, accm;
+      bias_pm(o, accp, accm);
+      es_walk_batched<EsTE8>(
+          0, 1, I, [&](int r) { return EsTE8{Tl[r * O + o], El[r * O + o]}; },
+          [&](EsTE8 w, int r) {
+            const float tw = bf2f(w.t), ew = fp8_byte(w.e);
+            accp = fmaf(tw + ew, xp[r], accp);
+            accm = fmaf(tw - ew, xm[r], accm);
+          });
+      yp[o] = do_act ? tanhf(accp) : accp;
+      ym[o] = do_act ? tanhf(accm) : accm;
+    }
+  }
+}
+
 // mlp_layers_pair with an fp8 (OCP e4m3fn) sigma*eps blob: one nt 16-B load
 // covers one octet of TWO consecutive i-rows (pheno_fp8_kernel's row-pair
 // interleave), halving both the bytes and the load count of the HBM eps
 // stream; theta stays bf16 (L2-resident). Same (oi, ip) tiling; the i-walk
 // is by row PAIRS, so the per-thread accumulation partition differs from
 // the bf16 path (documented; the fp8 path is new numerics regardless).
+//
+// STAGE (multi-step kernel, whose theta/eps rows cannot change during a
+// launch): the caller holds copies of small operands in LDS, filled once per
+// launch by mlp_pair_fp8_stage_fill, and the layers read them there instead
+// of taking a global round trip behind each layer's barrier.
+//   >= 1: sbias = every layer's bias start values, (tB + eB, tB - eB) per
+//         output, layer after layer;
+//   >= 2: the last layer's weights when it is on the scalar path (block-
+//         uniform `head_staged`): sht = its bf16 theta, she = its fp8 eps,
+//         element-ordered as in the blob.
+// Same values, same order of operations: outputs are those of STAGE 0.
+template <int STAGE = 0>
 __device__ __forceinline__ void mlp_layers_pair_fp8(
     const uint16_t* __restrict__ tb, const uint8_t* __restrict__ eb8,
     const MlpShape& sh, float* bufAp, float* bufAm, float* bufBp, float* bufBm,
     float* partial, int tid, int nthreads, int act_final,
-    float** xp_out, float** xm_out) {
+    float** xp_out, float** xm_out, const float* sbias = nullptr,
+    const uint16_t* sht = nullptr, const uint8_t* she = nullptr,
+    bool head_staged = false) {
   float* xp = bufAp;
   float* xm = bufAm;
   float* yp = bufBp;
@@ -467,6 +536,17 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
     const uint16_t* TBs = tb + sh.boff[l];
     const uint8_t* EBs8 = eb8 + sh.boff[l];
     const bool do_act = (l < sh.n_layers - 1) || act_final;
+    // start values of output o's two sums
+    auto bias_pm = [&](int o, float& sp, float& sm) {
+      if constexpr (STAGE >= 1) {
+        sp = sbias[2 * o];
+        sm = sbias[2 * o + 1];
+      } else {
+        const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
+        sp = tB + eB;
+        sm = tB - eB;
+      }
+    };
 
     if (sh.vec_ok[l]) {
       const int OCT = O >> 3;
@@ -616,8 +696,8 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
       }
       __syncthreads();
       for (int o = tid; o < O; o += nthreads) {
-        const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
-        float sp = tB + eB, sm = tB - eB;
+        float sp, sm;
+        bias_pm(o, sp, sm);
         const int oo = o >> 3, j = o & 7;
         for (int p = 0; p < PART; ++p) {
           sp += partial[(p * OCT + oo) * 8 + j];
@@ -628,8 +708,14 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
       }
     } else {
       // scalar path (small / odd layers): plain element-ordered fp8
+      bool staged = false;
+      if constexpr (STAGE >= 2) staged = head_staged && l == sh.n_layers - 1;
       const int PART = nthreads / O;
-      if (PART > 1) {
+      if (staged) {
+        if constexpr (STAGE >= 2)
+          mlp_pair_fp8_scalar_staged(sht, she, I, O, xp, xm, yp, ym, partial, partm, tid,
+                                     nthreads, do_act, bias_pm);
+      } else if (PART > 1) {
         const int oi = tid % O, ip = tid / O;
         float accp = 0.0f, accm = 0.0f;
         if (ip < PART) {
@@ -648,8 +734,8 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         }
         __syncthreads();
         for (int o = tid; o < O; o += nthreads) {
-          const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
-          float sp = tB + eB, sm = tB - eB;
+          float sp, sm;
+          bias_pm(o, sp, sm);
           for (int p = 0; p < PART; ++p) {
             sp += partial[p * O + o];
             sm += partm[p * O + o];
@@ -659,8 +745,8 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
         }
       } else {
         for (int o = tid; o < O; o += nthreads) {
-          const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
-          float accp = tB + eB, accm = tB - eB;
+          float accp, accm;
+          bias_pm(o, accp, accm);
           es_walk_batched<EsTE8>(
               0, 1, I,
               [&](int r) {
@@ -677,11 +763,52 @@ __device__ __forceinline__ void mlp_layers_pair_fp8(
       }
     }
     __syncthreads();
+    if constexpr (STAGE >= 1) sbias += 2 * O;
     float* t = xp; xp = yp; yp = t;
     t = xm; xm = ym; ym = t;
   }
   *xp_out = xp;
   *xm_out = xm;
+}
+
+// The stage of mlp_layers_pair_fp8<STAGE>: sizes (host) and the fill (once
+// per launch, every thread of the block; the caller's barrier follows).
+static inline int64_t mlp_pair_fp8_bias_floats(const MlpShape& sh) {
+  int64_t n = 0;
+  for (int l = 0; l < sh.n_layers; ++l) n += 2 * (int64_t)sh.dims[l + 1];
+  return n;
+}
+// elements of the last layer's weights if that layer is on the scalar path
+static inline int64_t mlp_pair_fp8_head_elems(const MlpShape& sh) {
+  const int l = sh.n_layers - 1;
+  return sh.vec_ok[l] ? 0 : (int64_t)sh.dims[l] * sh.dims[l + 1];
+}
+
+__device__ __forceinline__ void mlp_pair_fp8_stage_fill(
+    const uint16_t* __restrict__ tb, const uint8_t* __restrict__ eb8,
+    const MlpShape& sh, float* sbias, uint16_t* sht, uint8_t* she, bool head_staged,
+    int tid, int nthreads) {
+  for (int l = 0; l < sh.n_layers; ++l) {
+    const int O = sh.dims[l + 1];
+    const uint16_t* TBs = tb + sh.boff[l];
+    const uint8_t* EBs8 = eb8 + sh.boff[l];
+    for (int o = tid; o < O; o += nthreads) {
+      const float tB = bf2f(TBs[o]), eB = fp8_byte(EBs8[o]);
+      sbias[2 * o] = tB + eB;
+      sbias[2 * o + 1] = tB - eB;
+    }
+    sbias += 2 * O;
+  }
+  if (head_staged) {
+    const int l = sh.n_layers - 1;
+    const int n = sh.dims[l] * sh.dims[l + 1];
+    const uint16_t* Tt = tb + sh.woff[l];
+    const uint8_t* Et8 = eb8 + sh.woff[l];
+    for (int k = tid; k < n; k += nthreads) {
+      sht[k] = Tt[k];
+      she[k] = Et8[k];
+    }
+  }
 }
 
 __device__ __forceinline__ float es_actnoise(uint64_t seed, uint64_t ctr) {

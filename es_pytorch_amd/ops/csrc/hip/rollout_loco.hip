@@ -63,18 +63,37 @@ __device__ __forceinline__ void loco_build_obs(
   }
 }
 
+// LDS copies of operands that cannot change during a launch (the multi-step
+// fp8 pair kernel's STAGE levels): the step reads them here instead of taking
+// a global round trip behind a barrier. Laid out after the pair carve in this
+// order; `bias`, `ht`, `he` are mlp_layers_pair_fp8's stage.
+struct LocoStage {
+  const float *obmean, *obstd;     // D each
+  const float *b0, *wv, *wy, *wh;  // S each
+  const float* wa;                 // A
+  const float* bias;
+  const uint16_t* ht;
+  const uint8_t* he;
+  bool head;  // the last layer's weights are staged (level 2, scalar head)
+};
+
 // One obs pass for both members of a pair: obmean/obstd are loaded once and
 // both members' state loads issue together. Same per-member arithmetic as
-// loco_build_obs, division included.
+// loco_build_obs, division included. STAGE: obmean/obstd come from G.
+template <int STAGE = 0>
 __device__ __forceinline__ void loco_build_obs_pair(
     const LocoArgs& la, const LocoPtrs& P, int bp, int bm, float* bufAp, float* bufAm,
-    float* rawsP, float* rawsM, int tid, int nth) {
+    float* rawsP, float* rawsM, int tid, int nth, const LocoStage& G = LocoStage{}) {
   const int S = la.S;
   const float* sp = P.s_glob + (int64_t)bp * S;
   const float* sm = P.s_glob + (int64_t)bm * S;
+  const float* obmean;
+  const float* obstd;
+  if constexpr (STAGE >= 1) { obmean = G.obmean; obstd = G.obstd; }
+  else { obmean = P.obmean; obstd = P.obstd; }
   for (int i = tid; i < S; i += nth) {
     const float vp = sp[i], vm = sm[i];
-    const float mean = P.obmean[i], sd = P.obstd[i];
+    const float mean = obmean[i], sd = obstd[i];
     rawsP[i] = vp;
     rawsM[i] = vm;
     bufAp[i] = fclampf((vp - mean) / sd, -la.ob_clip, la.ob_clip);
@@ -83,7 +102,7 @@ __device__ __forceinline__ void loco_build_obs_pair(
   if (la.goal && tid < 2) {
     const float relp = (P.goal[(int64_t)bp * 2 + tid] - P.pos[(int64_t)bp * 3 + tid]) * 0.1f;
     const float relm = (P.goal[(int64_t)bm * 2 + tid] - P.pos[(int64_t)bm * 3 + tid]) * 0.1f;
-    const float mean = P.obmean[S + tid], sd = P.obstd[S + tid];
+    const float mean = obmean[S + tid], sd = obstd[S + tid];
     bufAp[S + tid] = fclampf((relp - mean) / sd, -la.ob_clip, la.ob_clip);
     bufAm[S + tid] = fclampf((relm - mean) / sd, -la.ob_clip, la.ob_clip);
   }
@@ -236,12 +255,23 @@ struct LocoBook {
 // Measured 0.1-0.5 us per step SLOWER than the reload at the flagship shape
 // (profiles/README.md, round 6), so es_loco_pair_episode_fp8 has it off by
 // default.
-template <int NM, bool CARRY = false>
+//
+// STAGE (never with CARRY): b0, wv, wy, wh and wa come from the LDS copies
+// in G instead of global memory.
+template <int NM, bool CARRY = false, int STAGE = 0>
 __device__ __forceinline__ void loco_dyn_finish_n(
     const LocoArgs& la, const LocoPtrs& P, const int* b, const float* const* raws,
     const float* const* abuf, float* const* part, int tid, int nth,
-    float* const* obs = nullptr, bool carry = false) {
+    float* const* obs = nullptr, bool carry = false,
+    const LocoStage& G = LocoStage{}) {
+  static_assert(!(CARRY && STAGE), "the staged levels do not carry");
   const int S = la.S, A = la.A;
+  const float *b0v, *wvv, *wyv, *whv, *wav;
+  if constexpr (STAGE >= 1) {
+    b0v = G.b0; wvv = G.wv; wyv = G.wy; whv = G.wh; wav = G.wa;
+  } else {
+    b0v = P.b0; wvv = P.wv; wyv = P.wy; whv = P.wh; wav = P.wa;
+  }
   float w_alive[NM];  // pre-step alive, used as obstat weight
   float *sb[NM], *ms[NM], *mq[NM];
 #pragma unroll
@@ -301,7 +331,7 @@ __device__ __forceinline__ void loco_dyn_finish_n(
     const int PART = oct8 ? nth / OCT : 0;
     for (int o = tid; o < S; o += nth) {
       // every load of this output whose address is known up front
-      const float b0o = P.b0[o], wvo = P.wv[o], wyo = P.wy[o], who = P.wh[o];
+      const float b0o = b0v[o], wvo = wvv[o], wyo = wyv[o], who = whv[o];
       float omean = 0.0f, osd = 1.0f;
       if constexpr (CARRY)
         if (carry) { omean = P.obmean[o]; osd = P.obstd[o]; }
@@ -370,7 +400,7 @@ __device__ __forceinline__ void loco_dyn_finish_n(
       }
     }
     for (int j = tid; j < A; j += nth) {
-      const float waj = P.wa[j];
+      const float waj = wav[j];
 #pragma unroll
       for (int m = 0; m < NM; ++m) {
         p0[m] = fmaf(0.5f * abuf[m][j], waj, p0[m]);
@@ -471,18 +501,18 @@ __device__ __forceinline__ void loco_dyn_finish(
 }
 
 // One fused epilogue for both members of a pair.
-template <bool CARRY = false>
+template <bool CARRY = false, int STAGE = 0>
 __device__ __forceinline__ void loco_dyn_finish_pair(
     const LocoArgs& la, const LocoPtrs& P, int bp, int bm, const float* rawsP,
     const float* rawsM, const float* abufP, const float* abufM, float* partP,
     float* partM, int tid, int nth, float* obsP = nullptr, float* obsM = nullptr,
-    bool carry = false) {
+    bool carry = false, const LocoStage& G = LocoStage{}) {
   const int bs[2] = {bp, bm};
   const float* const rs[2] = {rawsP, rawsM};
   const float* const as[2] = {abufP, abufM};
   float* const ps[2] = {partP, partM};
   float* const os[2] = {obsP, obsM};
-  loco_dyn_finish_n<2, CARRY>(la, P, bs, rs, as, ps, tid, nth, os, carry);
+  loco_dyn_finish_n<2, CARRY, STAGE>(la, P, bs, rs, as, ps, tid, nth, os, carry, G);
 }
 
 template <typename WT = uint16_t>
@@ -805,22 +835,23 @@ __device__ __forceinline__ void loco_dyn_partials_pair(
 // the optimizer cannot see through). CARRY: `have` = the previous step of
 // this launch left raws and the normalized obs in LDS, `keep` = this step
 // leaves them for the next (loco_dyn_finish_n); both block-uniform.
-template <typename EB, bool PIPE = true, bool CARRY = false>
+template <typename EB, bool PIPE = true, bool CARRY = false, int STAGE = 0>
 __device__ __forceinline__ void loco_pair_step_body(
     const MlpShape& sh, const LocoArgs& la, const LocoPtrs& P,
     const uint16_t* tb, const EB* eb, int bp, int bm, uint64_t salt,
     float* bufAp, float* bufAm, float* bufBp, float* bufBm, float* partial,
     float* rawsP, float* rawsM, float* abufP, float* abufM, int tid,
-    bool have = false, bool keep = false) {
+    bool have = false, bool keep = false, const LocoStage& G = LocoStage{}) {
   const int nth = blockDim.x;
   if (!(CARRY && have)) {
-    loco_build_obs_pair(la, P, bp, bm, bufAp, bufAm, rawsP, rawsM, tid, nth);
+    loco_build_obs_pair<STAGE>(la, P, bp, bm, bufAp, bufAm, rawsP, rawsM, tid, nth, G);
     __syncthreads();
   }
   float *ap, *am;
   if constexpr (sizeof(EB) == 1)
-    mlp_layers_pair_fp8(tb, (const uint8_t*)eb, sh, bufAp, bufAm, bufBp, bufBm,
-                        partial, tid, nth, 1, &ap, &am);
+    mlp_layers_pair_fp8<STAGE>(tb, (const uint8_t*)eb, sh, bufAp, bufAm, bufBp, bufBm,
+                               partial, tid, nth, 1, &ap, &am, G.bias, G.ht, G.he,
+                               G.head);
   else
     mlp_layers_pair(tb, (const uint16_t*)eb, sh, bufAp, bufAm, bufBp, bufBm,
                     partial, tid, nth, 1, &ap, &am);
@@ -830,8 +861,9 @@ __device__ __forceinline__ void loco_pair_step_body(
   if (la.S % 8 == 0)
     loco_dyn_partials_pair<PIPE>(P.Am, la.S, rawsP, rawsM, partial, partial + 2048,
                                  tid, nth);
-  loco_dyn_finish_pair<CARRY>(la, P, bp, bm, rawsP, rawsM, abufP, abufM, partial,
-                              partial + 2048, tid, nth, bufAp, bufAm, keep);
+  loco_dyn_finish_pair<CARRY, STAGE>(la, P, bp, bm, rawsP, rawsM, abufP, abufM,
+                                     partial, partial + 2048, tid, nth, bufAp, bufAm,
+                                     keep, G);
 }
 
 #define ES_LOCO_PAIR_CARVE()                                     \
@@ -901,13 +933,42 @@ loco_pair_episode_kernel(MlpShape sh, LocoArgs la, LocoPtrs P, const uint16_t* t
 // pointer, the slot indices and the thread index — through an empty asm the
 // optimizer cannot see through: a few scalar moves per step, and the body
 // compiles as it does in the per-step kernel. MINB = blocks per CU the
-// register budget is sized for (4: 128 VGPRs, 3: 134-135); none of the four
+// register budget is sized for (4: 128 VGPRs, 3: 134-138); none of the
 // instantiations spills or uses scratch. CARRY keeps the state and the next
 // observation in LDS between the steps of a launch (loco_dyn_finish_n); it
 // falls back to the reload when S % 8 != 0.
 #define ES_OPAQUE_S(x) asm volatile("" : "+s"(x))
 #define ES_OPAQUE_V(x) asm volatile("" : "+v"(x))
-template <int MINB, bool CARRY>
+// A pointer that crosses the asm as a pointer comes back generic: its loads
+// become flat_*, which count on vmcnt and lgkmcnt both, so every wait drains
+// the whole queue (vmcnt(0)) and the set rings are gone. It crosses as an
+// integer instead and is cast to the global address space on the way back;
+// null stays null.
+template <typename T>
+__device__ __forceinline__ T* es_opaque_global(T* p) {
+  unsigned long long v = (unsigned long long)p;
+  ES_OPAQUE_S(v);
+  return (T*)(__attribute__((address_space(1))) T*)v;
+}
+#define ES_OPAQUE_G(x) ((x) = es_opaque_global(x))
+
+// STAGE (with CARRY = false): what a block reads every step but nothing
+// writes during a launch is copied to LDS once, behind the pair carve, and
+// read there (LocoStage). 1: obmean, obstd, b0, wv, wy, wh, wa and the layer
+// biases; 2: also the last layer's weights when it is on the scalar path.
+// The launcher adds loco_stage_lds_bytes() and only picks a level at which
+// the whole grid is resident.
+static int64_t loco_stage_floats(const MlpShape& sh, const LocoArgs& la) {
+  return 2 * (int64_t)la.D + 4 * (int64_t)la.S + la.A + mlp_pair_fp8_bias_floats(sh);
+}
+static unsigned loco_stage_lds_bytes(const MlpShape& sh, const LocoArgs& la, int level) {
+  if (level < 1) return 0;
+  int64_t n = 4 * loco_stage_floats(sh, la);
+  if (level >= 2) n += 3 * mlp_pair_fp8_head_elems(sh);  // bf16 theta + fp8 eps
+  return (unsigned)((n + 15) & ~(int64_t)15);
+}
+
+template <int MINB, bool CARRY, int STAGE = 0>
 __global__ void __launch_bounds__(256, MINB)
 loco_pair_chunk_fp8_kernel(MlpShape sh, LocoArgs la, LocoPtrs Pk, const uint16_t* tb,
                            const uint8_t* eb, int n_pairs, int n_steps, int salt_base) {
@@ -916,25 +977,57 @@ loco_pair_chunk_fp8_kernel(MlpShape sh, LocoArgs la, LocoPtrs Pk, const uint16_t
   int bpl = bp, bml = bm;
   int tid = threadIdx.x;
   const bool oct8 = (la.S % 8 == 0);
+  LocoStage G = {};
+  if constexpr (STAGE >= 1) {
+    float* g = abufM + 64;  // end of the pair carve
+    float* gmean = g;
+    float* gstd = gmean + la.D;
+    float* gb0 = gstd + la.D;
+    float* gwv = gb0 + la.S;
+    float* gwy = gwv + la.S;
+    float* gwh = gwy + la.S;
+    float* gwa = gwh + la.S;
+    float* gbias = gwa + la.A;
+    int nb = 0;
+    for (int l = 0; l < sh.n_layers; ++l) nb += 2 * sh.dims[l + 1];
+    const int hl = sh.n_layers - 1;
+    uint16_t* ght = reinterpret_cast<uint16_t*>(gbias + nb);
+    uint8_t* ghe = reinterpret_cast<uint8_t*>(ght + sh.dims[hl] * sh.dims[hl + 1]);
+    const bool head = STAGE >= 2 && !sh.vec_ok[hl];
+    for (int i = tid; i < la.D; i += 256) {
+      gmean[i] = Pk.obmean[i];
+      gstd[i] = Pk.obstd[i];
+    }
+    for (int i = tid; i < la.S; i += 256) {
+      gb0[i] = Pk.b0[i];
+      gwv[i] = Pk.wv[i];
+      gwy[i] = Pk.wy[i];
+      gwh[i] = Pk.wh[i];
+    }
+    for (int i = tid; i < la.A; i += 256) gwa[i] = Pk.wa[i];
+    mlp_pair_fp8_stage_fill(tb, ebp, sh, gbias, ght, ghe, head, tid, 256);
+    __syncthreads();
+    G = LocoStage{gmean, gstd, gb0, gwv, gwy, gwh, gwa, gbias, ght, ghe, head};
+  }
 #pragma clang loop unroll(disable)
   for (int t = 1; t <= n_steps; ++t) {
-    ES_OPAQUE_S(P.weights); ES_OPAQUE_S(P.obmean); ES_OPAQUE_S(P.obstd);
-    ES_OPAQUE_S(P.ac_std_dev); ES_OPAQUE_S(P.seed_dev); ES_OPAQUE_S(P.s_glob);
-    ES_OPAQUE_S(P.pos); ES_OPAQUE_S(P.goal); ES_OPAQUE_S(P.Bm); ES_OPAQUE_S(P.b0);
-    ES_OPAQUE_S(P.wv); ES_OPAQUE_S(P.wa); ES_OPAQUE_S(P.wy); ES_OPAQUE_S(P.wh);
-    ES_OPAQUE_S(P.Am); ES_OPAQUE_S(P.alive); ES_OPAQUE_S(P.rew_total);
-    ES_OPAQUE_S(P.member_steps); ES_OPAQUE_S(P.behv); ES_OPAQUE_S(P.mo_sum);
-    ES_OPAQUE_S(P.mo_sumsq);
-    ES_OPAQUE_S(tb); ES_OPAQUE_S(ebp); ES_OPAQUE_S(bpl); ES_OPAQUE_S(bml);
+    ES_OPAQUE_G(P.weights); ES_OPAQUE_G(P.obmean); ES_OPAQUE_G(P.obstd);
+    ES_OPAQUE_G(P.ac_std_dev); ES_OPAQUE_G(P.seed_dev); ES_OPAQUE_G(P.s_glob);
+    ES_OPAQUE_G(P.pos); ES_OPAQUE_G(P.goal); ES_OPAQUE_G(P.Bm); ES_OPAQUE_G(P.b0);
+    ES_OPAQUE_G(P.wv); ES_OPAQUE_G(P.wa); ES_OPAQUE_G(P.wy); ES_OPAQUE_G(P.wh);
+    ES_OPAQUE_G(P.Am); ES_OPAQUE_G(P.alive); ES_OPAQUE_G(P.rew_total);
+    ES_OPAQUE_G(P.member_steps); ES_OPAQUE_G(P.behv); ES_OPAQUE_G(P.mo_sum);
+    ES_OPAQUE_G(P.mo_sumsq); ES_OPAQUE_G(tb); ES_OPAQUE_G(ebp);
+    ES_OPAQUE_S(bpl); ES_OPAQUE_S(bml);
     ES_OPAQUE_V(tid);
     // 1 - leak and -ob_clip are otherwise computed once and held in VGPRs
     // (the last 4 spilled registers of the 4-block variant). Laundering the
     // LDS pointers or the integer members of `la` as well brings spills back.
     ES_OPAQUE_S(la.leak); ES_OPAQUE_S(la.ob_clip);
-    loco_pair_step_body<uint8_t, true, CARRY>(
+    loco_pair_step_body<uint8_t, true, CARRY, STAGE>(
         sh, la, P, tb, ebp, bpl, bml, (uint64_t)(salt_base + t), bufAp, bufAm, bufBp,
         bufBm, partial, rawsP, rawsM, abufP, abufM, tid, oct8 && t > 1,
-        oct8 && t < n_steps);
+        oct8 && t < n_steps, G);
   }
 }
 
@@ -1035,18 +1128,29 @@ static int loco_launch_episode(LocoLaunch& L, int32_t n_steps, int32_t member_ba
 // fp8 sibling or the episode kernel (tail = n_steps, salt_base); EB is the
 // element type of its eps rows. Grid = n_pairs * eps blocks, each evaluating
 // the +/- slots of one (pair, episode).
+// `lds` = dynamic LDS bytes: the pair carve, plus the stage of the multi-step
+// fp8 kernel's staged levels.
+template <typename EB, typename... Tail>
+static int loco_launch_pair_lds(void (*kern)(MlpShape, LocoArgs, LocoPtrs,
+                                             const uint16_t*, const EB*, int, Tail...),
+                                const LocoLaunch& L, const void* theta_row,
+                                const void* eps_rows, int32_t n_pairs, void* stream,
+                                unsigned lds, Tail... tail) {
+  const unsigned grid = (unsigned)(n_pairs * L.la.eps);
+  kern<<<dim3(grid), dim3(256), lds, (hipStream_t)stream>>>(
+      L.sh, L.la, L.P, (const uint16_t*)theta_row, (const EB*)eps_rows, n_pairs, tail...);
+  ES_CHECK_LAUNCH();
+  return 0;
+}
+
 template <typename EB, typename... Tail>
 static int loco_launch_pair(void (*kern)(MlpShape, LocoArgs, LocoPtrs, const uint16_t*,
                                          const EB*, int, Tail...),
                             const LocoLaunch& L, const void* theta_row,
                             const void* eps_rows, int32_t n_pairs, void* stream,
                             Tail... tail) {
-  const unsigned lds = (unsigned)mlp_pair_lds_bytes(L.sh.maxdim, L.la.S);
-  const unsigned grid = (unsigned)(n_pairs * L.la.eps);
-  kern<<<dim3(grid), dim3(256), lds, (hipStream_t)stream>>>(
-      L.sh, L.la, L.P, (const uint16_t*)theta_row, (const EB*)eps_rows, n_pairs, tail...);
-  ES_CHECK_LAUNCH();
-  return 0;
+  return loco_launch_pair_lds(kern, L, theta_row, eps_rows, n_pairs, stream,
+                              (unsigned)mlp_pair_lds_bytes(L.sh.maxdim, L.la.S), tail...);
 }
 
 extern "C" int es_loco_step(const void* weights, const void* obmean, const void* obstd,
@@ -1188,17 +1292,100 @@ extern "C" int es_loco_pair_episode(
 #define ES_CHUNK_FP8_CARRY 0
 static int g_chunk_fp8_min_blocks = ES_CHUNK_FP8_MIN_BLOCKS;
 static int g_chunk_fp8_carry = ES_CHUNK_FP8_CARRY;
+// STAGE level: -1 = automatic, the highest level up to g_chunk_fp8_stage_max
+// at which every block of the grid is resident (blocks retire only at the end
+// of the launch, and the stage costs LDS, hence blocks per CU); 0/1/2 force a
+// level. CARRY builds have no staged form and run level 0. The automatic
+// choice is capped at level 0: staging measured +2.0 % per flagship
+// generation, every run ahead of every unstaged one, but short of the
+// project's bar of three times the run-to-run spread (profiles/README.md,
+// round 7). -DES_CHUNK_FP8_STAGE_MAX=2 builds a library that stages by default
+// (tools/build_variants.py), es_loco_pair_episode_fp8_stage_max sets it at
+// run time.
+#ifndef ES_CHUNK_FP8_STAGE_MAX
+#define ES_CHUNK_FP8_STAGE_MAX 0
+#endif
+static int g_chunk_fp8_stage = -1;
+static int g_chunk_fp8_stage_max = ES_CHUNK_FP8_STAGE_MAX;
 
-// min_blocks = 0 restores the defaults.
+// min_blocks = 0 restores the defaults, the automatic stage level included.
 extern "C" int es_loco_pair_episode_fp8_config(int32_t min_blocks, int32_t carry) {
   if (min_blocks == 0) {
     min_blocks = ES_CHUNK_FP8_MIN_BLOCKS;
     carry = ES_CHUNK_FP8_CARRY;
+    g_chunk_fp8_stage = -1;
+    g_chunk_fp8_stage_max = ES_CHUNK_FP8_STAGE_MAX;
   }
   if (min_blocks != 3 && min_blocks != 4) return -108;
   g_chunk_fp8_min_blocks = min_blocks;
   g_chunk_fp8_carry = carry != 0;
   return 0;
+}
+
+// level: -1 automatic (the default), 0/1/2 forced. A forced level at which
+// the grid is not resident makes es_loco_pair_episode_fp8 return -110.
+extern "C" int es_loco_pair_episode_fp8_stage(int32_t level) {
+  if (level < -1 || level > 2) return -109;
+  g_chunk_fp8_stage = level;
+  return 0;
+}
+
+// highest level the automatic choice may take (0..2)
+extern "C" int es_loco_pair_episode_fp8_stage_max(int32_t max_level) {
+  if (max_level < 0 || max_level > 2) return -109;
+  g_chunk_fp8_stage_max = max_level;
+  return 0;
+}
+
+// the level es_loco_pair_episode_fp8 launched last (tests, tools/kbench.py)
+static int g_chunk_fp8_last_stage = 0;
+extern "C" int es_loco_pair_episode_fp8_last_stage() { return g_chunk_fp8_last_stage; }
+
+typedef void (*ChunkFp8Kern)(MlpShape, LocoArgs, LocoPtrs, const uint16_t*,
+                             const uint8_t*, int, int, int);
+static ChunkFp8Kern chunk_fp8_kernel(bool four, bool carry, int stage) {
+  if (carry)
+    return four ? loco_pair_chunk_fp8_kernel<4, true> : loco_pair_chunk_fp8_kernel<3, true>;
+  switch (stage) {
+    case 2:
+      // one build for both settings: under the 4-block budget level 2
+      // spills (2 VGPRs, 12 B per lane of scratch); at the flagship shape its
+      // LDS holds 3 blocks per CU in any case
+      return loco_pair_chunk_fp8_kernel<3, false, 2>;
+    case 1:
+      return four ? loco_pair_chunk_fp8_kernel<4, false, 1>
+                  : loco_pair_chunk_fp8_kernel<3, false, 1>;
+    default:
+      return four ? loco_pair_chunk_fp8_kernel<4, false>
+                  : loco_pair_chunk_fp8_kernel<3, false>;
+  }
+}
+
+// Blocks of `kern` (256 threads, `lds` dynamic bytes) the current device
+// holds at once: the occupancy query times the CU count, 0 where it cannot
+// launch at all. Remembered per (kernel, lds, device): the engine asks the
+// same question every launch.
+static int64_t chunk_fp8_resident(ChunkFp8Kern kern, unsigned lds) {
+  struct Memo { ChunkFp8Kern kern; unsigned lds; int dev; int64_t n; };
+  static Memo memo[8];
+  static int n_memo = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  for (int i = 0; i < n_memo; ++i)
+    if (memo[i].kern == kern && memo[i].lds == lds && memo[i].dev == dev) return memo[i].n;
+  int cus = 0, per_cu = 0;
+  int64_t n = 0;
+  if (lds <= 64 * 1024 &&
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) == hipSuccess)
+    n = (int64_t)per_cu * cus;
+  else
+    (void)hipGetLastError();
+  static int next = 0;
+  memo[next] = Memo{kern, lds, dev, n};
+  next = (next + 1) % 8;
+  if (n_memo < 8) ++n_memo;
+  return n;
 }
 
 // fp8-eps pair-episode: the argument list of es_loco_pair_episode; eps_rows
@@ -1223,12 +1410,24 @@ extern "C" int es_loco_pair_episode_fp8(
                       leak, ctrl, alive_bonus, fall_thr, dt);
   if (rc) return rc;
   const bool four = g_chunk_fp8_min_blocks == 4, carry = g_chunk_fp8_carry != 0;
-  auto* kern = four ? (carry ? loco_pair_chunk_fp8_kernel<4, true>
-                             : loco_pair_chunk_fp8_kernel<4, false>)
-                    : (carry ? loco_pair_chunk_fp8_kernel<3, true>
-                             : loco_pair_chunk_fp8_kernel<3, false>);
-  return loco_launch_pair(kern, L, theta_row, eps_rows, n_pairs, stream, n_steps,
-                          salt_base);
+  const int64_t grid = (int64_t)n_pairs * L.la.eps;
+  const unsigned lds0 = (unsigned)mlp_pair_lds_bytes(L.sh.maxdim, L.la.S);
+  int level = 0;
+  if (!carry) {
+    const int forced = g_chunk_fp8_stage;
+    for (level = forced < 0 ? g_chunk_fp8_stage_max : forced; level > 0; --level) {
+      const unsigned lds = lds0 + loco_stage_lds_bytes(L.sh, L.la, level);
+      if (chunk_fp8_resident(chunk_fp8_kernel(four, false, level), lds) >= grid) break;
+      if (forced >= 0) return -110;  // a forced level must hold the whole grid
+    }
+  } else if (g_chunk_fp8_stage > 0) {
+    return -110;
+  }
+  g_chunk_fp8_last_stage = level;
+  return loco_launch_pair_lds(chunk_fp8_kernel(four, carry, level), L, theta_row,
+                              eps_rows, n_pairs, stream,
+                              lds0 + loco_stage_lds_bytes(L.sh, L.la, level), n_steps,
+                              salt_base);
 }
 
 extern "C" int es_loco_episode(const void* weights, const void* obmean, const void* obstd,

@@ -14,6 +14,10 @@ innermost ones, and the own blocks of loops that hold others) prints
     python tools/isa_loops.py es_pytorch_amd/ops/csrc/hip/rollout_loco.hip \
         loco_pair_step_fp8_kernel [--min-len 40] [-D NAME=VALUE]
 
+With --summary it prints, for every kernel whose name holds the given string
+(each instantiation of a template), the memory instructions by segment (flat,
+global, scratch, ds) and the histogram of s_waitcnt forms.
+
 It is a reading aid: it reports ordinary opcodes and checks nothing.
 """
 import argparse
@@ -138,6 +142,48 @@ def report(name, depth, inner, ins, top):
     print(f"   global_load {nload}; timeline: {line or '-'}")
 
 
+_SEGMENTS = ("flat", "global", "scratch", "ds")
+_WAIT_ARG = re.compile(r"(vmcnt|lgkmcnt|expcnt)\((\d+)\)")
+
+
+def kernel_names(lines, kernel):
+    """Mangled labels of every function whose name contains `kernel`."""
+    return [ln.split(":")[0] for ln in lines
+            if re.match(r"^[A-Za-z_]\w*:", ln) and kernel in ln.split(":")[0]]
+
+
+def summary(body):
+    """(memory instructions by segment, histogram of s_waitcnt forms) of one
+    kernel: {segment: Counter(opcode)}, Counter('vmcnt(3) lgkmcnt(0)')."""
+    mem = {s: collections.Counter() for s in _SEGMENTS}
+    waits = collections.Counter()
+    for op, rest in insns(body, [(0, len(body) - 1)]):
+        seg = op.split("_", 1)[0]
+        if seg in mem and "_" in op:
+            mem[seg][op] += 1
+        elif op == "s_waitcnt":
+            form = " ".join(f"{k}({n})" for k, n in _WAIT_ARG.findall(rest))
+            waits[form or rest.strip()] += 1
+    return mem, waits
+
+
+def report_summary(label, body):
+    mem, waits = summary(body)
+    print(f"{label}:")
+    for seg in _SEGMENTS:
+        ops = ", ".join(f"{op} {c}" for op, c in sorted(mem[seg].items()))
+        print(f"   {seg:8s}{sum(mem[seg].values()):5d}  {ops}")
+    vm = collections.Counter()
+    for form, c in waits.items():
+        m = _VMCNT.search(form)
+        if m:
+            vm["vmcnt(0)" if m.group(1) == "0" else "vmcnt(n>0)"] += c
+    print(f"   s_waitcnt {sum(waits.values())}: " +
+          "  ".join(f"{k} {c}" for k, c in sorted(vm.items())))
+    for form, c in sorted(waits.items(), key=lambda kv: (-kv[1], kv[0])):
+        print(f"   {c:5d}  {form}")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("src")
@@ -149,6 +195,10 @@ def main():
                     help="preprocessor definition passed to hipcc, e.g. -D NDEBUG=1")
     ap.add_argument("--has", default="",
                     help="only loops holding an opcode with this prefix")
+    ap.add_argument("--summary", action="store_true",
+                    help="for every kernel whose name holds KERNEL: memory "
+                         "instructions by segment (flat, global, scratch, ds) and "
+                         "the histogram of s_waitcnt forms, instead of the loops")
     ap.add_argument("--asm", help="read this assembly file instead of compiling")
     a = ap.parse_args()
     if a.asm:
@@ -156,6 +206,12 @@ def main():
             lines = f.read().splitlines()
     else:
         lines = compile_asm(a.src, [f"-D{d}" for d in a.defs])
+    if a.summary:
+        for name in kernel_names(lines, a.kernel):
+            res = resources(lines, name)
+            report_summary(name + "  " + "  ".join(f"{k}={v}" for k, v in res.items()),
+                           kernel_body(lines, name))
+        return
     res = resources(lines, a.kernel)
     print(f"{a.kernel}: " + "  ".join(f"{k}={v}" for k, v in res.items()))
     body = kernel_body(lines, a.kernel)

@@ -38,6 +38,11 @@ def main():
                    help="fp8 multi-step kernel: blocks per CU it is sized for")
     p.add_argument("--chunk-carry", type=int, default=None, choices=[0, 1],
                    help="fp8 multi-step kernel: keep the state in LDS between steps")
+    p.add_argument("--chunk-stage", type=int, default=None, choices=[-1, 0, 1, 2],
+                   help="fp8 multi-step kernel: level of launch invariants staged "
+                        "in LDS (-1 automatic, the default; needs --chunk-carry 0)")
+    p.add_argument("--chunk-stage-max", type=int, default=None, choices=[0, 1, 2],
+                   help="highest level the automatic choice may take")
     args = p.parse_args()
 
     from es_pytorch_amd.config import AttrDict
@@ -56,6 +61,14 @@ def main():
             3 if args.chunk_blocks is None else args.chunk_blocks,
             1 if args.chunk_carry is None else args.chunk_carry),
             "es_loco_pair_episode_fp8_config")
+    if args.chunk_stage is not None:
+        from es_pytorch_amd import ops
+        ops.check(ops.hip().es_loco_pair_episode_fp8_stage(args.chunk_stage),
+                  "es_loco_pair_episode_fp8_stage")
+    if args.chunk_stage_max is not None:
+        from es_pytorch_amd import ops
+        ops.check(ops.hip().es_loco_pair_episode_fp8_stage_max(args.chunk_stage_max),
+                  "es_loco_pair_episode_fp8_stage_max")
     dev = torch.device("cuda", 0)
     comm = Comm(dev)
     torch.manual_seed(0)
@@ -87,7 +100,11 @@ def main():
     eng.step(ranker)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(f"gen: {dt*1e3:.2f} ms  per-step: {dt/args.steps*1e6:.1f} us  "
+    stage = ""
+    if args.fp8 and args.pair and args.chunk > 1:
+        from es_pytorch_amd import ops
+        stage = f"chunk-stage={ops.hip().es_loco_pair_episode_fp8_last_stage()}  "
+    print(f"gen: {dt*1e3:.2f} ms  per-step: {dt/args.steps*1e6:.1f} us  {stage}"
           f"numerics={eng.numerics} timings={eng.timings}")
 
 
