@@ -17,11 +17,18 @@ Unlike the reference (which evaluates the SAME +noise phenotypes twice —
 ``multi_agent.py:48-49``, a documented quirk), this engine uses true
 antithetic pairs: instance slots [0, pairs) carry +noise for every policy
 and [pairs, 2*pairs) carry -noise; slot 2*pairs is the all-noiseless game.
+
+Two rollout modes. ``"step"`` (the default) is the loop described above.
+``"episode"`` (``rollout_mode=`` or ``general.ma_rollout_mode``) plays the
+whole rollout of a generation in ONE launch of the fused tag kernel
+(``rollout_tag.hip``): both policies' forwards, the env step and the
+bookkeeping per game, with games that end leaving early. It draws the same
+action noise as the step loop and needs the ``BatchedPursuitTag`` env on a GPU.
 """
 from __future__ import annotations
 
 import time
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -30,6 +37,7 @@ from es_pytorch_amd import ops
 from es_pytorch_amd.core.engine import forward_perm
 from es_pytorch_amd.core.noisetable import NoiseTable
 from es_pytorch_amd.core.policy import Policy
+from es_pytorch_amd.envs.multiagent import BatchedPursuitTag
 from es_pytorch_amd.nn.obstat import ObStat
 from es_pytorch_amd.nn.optimizers import Adam
 from es_pytorch_amd.parallel.comm import Comm
@@ -78,7 +86,7 @@ class _PolicyState:
 
 class MultiAgentGpuEngine:
     def __init__(self, cfg, comm: Comm, policies: List[Policy], nt: NoiseTable, env,
-                 rs: np.random.RandomState):
+                 rs: np.random.RandomState, rollout_mode: Optional[str] = None):
         self.cfg = cfg
         self.comm = comm
         self.nt = nt
@@ -87,6 +95,24 @@ class MultiAgentGpuEngine:
         self.device = nt.noise.device
         self.n_agents = len(policies)
         assert env.N_AGENTS == self.n_agents
+        if rollout_mode is None:
+            rollout_mode = cfg.general.get("ma_rollout_mode", "step")
+        if rollout_mode not in ("step", "episode"):
+            raise ValueError(f"ma_rollout_mode must be 'step' or 'episode', got "
+                             f"{rollout_mode!r}")
+        if rollout_mode == "episode":
+            # the fused kernel IS the tag game: fail here, not mid-generation
+            if not isinstance(env, BatchedPursuitTag):
+                raise ValueError(
+                    f"ma_rollout_mode='episode' runs the fused PursuitTag kernel "
+                    f"(ops/csrc/hip/rollout_tag.hip) and needs a BatchedPursuitTag "
+                    f"env, got {type(env).__name__} - use ma_rollout_mode='step'")
+            if self.device.type != "cuda" or env.device.type != "cuda":
+                raise ValueError(
+                    f"ma_rollout_mode='episode' needs the noise table and the env "
+                    f"on a GPU, got {self.device.type!r} and {env.device.type!r} - "
+                    f"use ma_rollout_mode='step'")
+        self.rollout_mode = rollout_mode
 
         ppg = cfg.general.policies_per_gen
         assert ppg % comm.size == 0 and (ppg / comm.size) % 2 == 0
@@ -104,6 +130,11 @@ class MultiAgentGpuEngine:
         self.member_steps = torch.zeros(self.B, dtype=torch.float32, device=self.device)
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.max_steps = int(cfg.env.max_steps)
+        if rollout_mode == "episode":
+            # per-game fp64 observation moments, (game, agent, ob)
+            self.ep_ob_sum = torch.zeros((self.B, self.n_agents, env.ob_dims[0]),
+                                         dtype=torch.float64, device=self.device)
+            self.ep_ob_sumsq = torch.zeros_like(self.ep_ob_sum)
         self.gen = 0
         self.timings = {}
 
@@ -122,6 +153,29 @@ class MultiAgentGpuEngine:
             st.row_stride, 1, self.B - 1, 0, 1, 0, None, None,
             self._stream()), "es_mlp_fwd")
         return self.actions[i]
+
+    def _rollout_episode(self):
+        """The whole rollout in one launch, on the env's own p/v tensors."""
+        s0, s1 = self.states
+        env = self.env
+        assert env.p.is_contiguous() and env.v.is_contiguous()
+        self.ep_ob_sum.zero_()
+        self.ep_ob_sumsq.zero_()
+        ops.check(ops.hip().es_tag_episode(
+            env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
+            self.member_steps.data_ptr(), self.rew_total.data_ptr(),
+            self.ep_ob_sum.data_ptr(), self.ep_ob_sumsq.data_ptr(),
+            s0.weights.data_ptr(), s1.weights.data_ptr(), s0.obmean.data_ptr(),
+            s1.obmean.data_ptr(), s0.obstd.data_ptr(), s1.obstd.data_ptr(),
+            s0.dims_arr.ctypes.data, len(s0.dims_arr), s1.dims_arr.ctypes.data,
+            len(s1.dims_arr), s0.row_stride, s1.row_stride,
+            float(s0.policy._module.ob_clip), float(s1.policy._module.ob_clip),
+            s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(), self.seed_dev.data_ptr(),
+            0, self.n_agents, env.ob_dims[0], self.B, self.max_steps, 1, self.B - 1,
+            self._stream()), "es_tag_episode")
+        ob_sums = [self.ep_ob_sum[:, i].sum(0) for i in range(self.n_agents)]
+        ob_sumsqs = [self.ep_ob_sumsq[:, i].sum(0) for i in range(self.n_agents)]
+        return ob_sums, ob_sumsqs, self.member_steps.sum().double()
 
     def step(self, rankers: List[Ranker]) -> Tuple[List[float], List[ObStat]]:
         """One co-evolution generation; every policy updated from its own
@@ -147,17 +201,20 @@ class MultiAgentGpuEngine:
         ob_sumsqs = [torch.zeros_like(s) for s in ob_sums]
         ob_count = torch.zeros((), dtype=torch.float64, device=self.device)
 
-        for t in range(self.max_steps):
-            acts = [self._forward(i, obs[i], t + 1) for i in range(self.n_agents)]
-            obs, rews, done = self.env.step(acts)
-            self.rew_total.add_(rews * self.alive.unsqueeze(1))
-            self.member_steps.add_(self.alive)
-            w = self.alive.unsqueeze(1)
-            for i in range(self.n_agents):
-                ob_sums[i].add_((obs[i] * w).sum(0).double())
-                ob_sumsqs[i].add_((obs[i] * obs[i] * w).sum(0).double())
-            ob_count.add_(self.alive.sum().double())
-            self.alive.mul_(1.0 - done.float())
+        if self.rollout_mode == "episode":
+            ob_sums, ob_sumsqs, ob_count = self._rollout_episode()
+        else:
+            for t in range(self.max_steps):
+                acts = [self._forward(i, obs[i], t + 1) for i in range(self.n_agents)]
+                obs, rews, done = self.env.step(acts)
+                self.rew_total.add_(rews * self.alive.unsqueeze(1))
+                self.member_steps.add_(self.alive)
+                w = self.alive.unsqueeze(1)
+                for i in range(self.n_agents):
+                    ob_sums[i].add_((obs[i] * w).sum(0).double())
+                    ob_sumsqs[i].add_((obs[i] * obs[i] * w).sum(0).double())
+                ob_count.add_(self.alive.sum().double())
+                self.alive.mul_(1.0 - done.float())
 
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)

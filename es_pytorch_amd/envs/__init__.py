@@ -29,6 +29,10 @@ def make_batched(name: str, batch: int, device="cpu", **kwargs) -> BatchedEnv:
         return BatchedCartPole(batch, device)
     if c == "Pendulum":
         return BatchedPendulum(batch, device)
+    if c in ("PursuitTag", "Tag"):
+        # the two-agent game of the co-evolution engine (core/ma_engine.py)
+        from es_pytorch_amd.envs.multiagent import BatchedPursuitTag
+        return BatchedPursuitTag(batch, device, **kwargs)
     if c in ("HumanoidFlagrun", "HumanoidFlagrunHarder"):
         kwargs.setdefault("goal_conditioned", True)
         return SyntheticLocomotion("HumanoidFlagrun", batch, device, **kwargs)

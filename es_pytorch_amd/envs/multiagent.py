@@ -142,6 +142,11 @@ class BatchedPursuitTag:
         return self._obs(), rews, done
 
     @property
+    def ob_dim(self):
+        """Per-agent observation width (both agents see 8)."""
+        return self.ob_dims[0]
+
+    @property
     def positions(self):
         import torch
         return torch.cat([self.p[:, 0],

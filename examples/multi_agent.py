@@ -134,7 +134,11 @@ def main_gpu(cfg, comm, rs):
                                                        cfg.policy.lr)))
     nt = NoiseTable.create_shared(comm, cfg.noise.tbl_size, len(policies[0]),
                                   reporter, cfg.general.seed, device=comm.device)
-    engine = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs)
+    # general.ma_rollout_mode: "step" (default) or "episode", the fused
+    # whole-episode kernel (configs/multi_agent_fused.json)
+    engine = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs,
+                                 rollout_mode=cfg.general.get("ma_rollout_mode"))
+    reporter.print(f"rollout mode: {engine.rollout_mode}")
     for gen in range(cfg.general.gens):
         reporter.start_gen()
         rankers = [CenteredRanker() for _ in range(env.N_AGENTS)]
