@@ -21,7 +21,9 @@ One rank = one GPU; per generation:
    every generation (launch-overhead-free inner loop; SURVEY.md §7.2 step 2);
    finished episodes stay in the batch under an ``alive`` mask with their
    rewards/behaviour frozen, matching the reference's break-on-done
-   (``gym_runner.py:63-64``);
+   (``gym_runner.py:63-64``); ``classic_fused`` (opt-in) plays CartPole and
+   Pendulum rollouts in ONE whole-episode launch instead
+   (``rollout_classic.hip``), ended slots leaving the kernel's loop;
 4. (fit+, fit-, idx) fp64 triples go through ONE RCCL all_gather over xGMI
    (replaces the replicated Alltoall, ``es.py:84-95``); ranking runs
    redundantly on every rank (reference README.md:10-12 — parameters are
@@ -97,7 +99,8 @@ class GpuEngine:
                  split_dyn: Optional[bool] = None,
                  pair_rollout: Optional[bool] = None,
                  eps_fp8: Optional[bool] = None,
-                 weights_dtype: Optional[str] = None):
+                 weights_dtype: Optional[str] = None,
+                 classic_fused: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -333,6 +336,39 @@ class GpuEngine:
             self._one_signs = torch.ones(self.pairs, dtype=torch.float32, device=d)
         self._warned_host_ranker = False
 
+        # whole-episode kernel for the classic-control envs (rollout_classic.hip):
+        # ONE launch per generation instead of max_steps x (forward + a dozen
+        # torch kernels), slots whose episode ends leave the loop. Opt-in;
+        # `fused` keeps meaning the locomotion path.
+        if classic_fused is None:
+            classic_fused = bool(cfg.general.get("classic_fused", False))
+        self.classic_fused = bool(classic_fused)
+        if self.classic_fused:
+            self._classic_check()
+            # per-slot moments: the kernel accumulates each slot's own, the
+            # save_mask weighting happens at reduction time
+            self.cl_ob_sum = torch.zeros((self.B, D), dtype=torch.float64, device=d)
+            self.cl_ob_sumsq = torch.zeros((self.B, D), dtype=torch.float64, device=d)
+
+    def _classic_check(self):
+        """classic_fused=True on something the kernel does not cover fails
+        here, at construction, not with a kernel error code mid-generation."""
+        from es_pytorch_amd.envs.classic import BatchedCartPole, BatchedPendulum
+        env = self.env
+        if not isinstance(env, (BatchedCartPole, BatchedPendulum)):
+            raise ValueError(
+                f"classic_fused covers BatchedCartPole and BatchedPendulum only, got "
+                f"{type(env).__name__}")
+        if self.device.type != "cuda" or torch.device(env.device).type != "cuda":
+            raise ValueError(
+                "classic_fused runs a HIP kernel on the env's own tensors: the noise "
+                "table and the env must both be on a GPU")
+        if self.bins > 1 or self.act_mode != 0:
+            raise ValueError(
+                "classic_fused supports the plain action head only (no FFBinned, no "
+                "FFIntegGausAction* policy)")
+        self._classic_kind = 0 if isinstance(env, BatchedCartPole) else 1
+
     @staticmethod
     def _fp8_layout_ok(dims: List[int]) -> bool:
         """Mirror of the fp8 row-pair interleave constraints (pheno.hip):
@@ -362,7 +398,8 @@ class GpuEngine:
         if self.pair_rollout:
             path, enc = "pair", "e4m3" if self.eps_fp8 else "bf16"
         else:
-            path = "split" if self.split_dyn else "fused" if self.fused else "generic"
+            path = "split" if self.split_dyn else "fused" if self.fused else \
+                "classic" if self.classic_fused else "generic"
             enc = "none"
         return {"weights": self.weights_dtype, "eps_encoding": enc, "path": path,
                 "rollout_mode": self.rollout_mode}
@@ -550,6 +587,29 @@ class GpuEngine:
             self._loco_episode((self.M - 1) * self.eps, self.eps, 0,
                                block_threads=512)
 
+    def _classic_episode(self):
+        """The whole episode of all B slots in ONE launch, on the env's own
+        state tensors; fills behv from them afterwards (they hold each slot's
+        state at its last live step)."""
+        env = self.env
+        if self._classic_kind == 0:
+            state, state2 = env.state.data_ptr(), None
+        else:
+            state, state2 = env.th.data_ptr(), env.thdot.data_ptr()
+        fn, name = (ops.hip().es_classic_episode_f32, "es_classic_episode_f32") \
+            if self.fp32 else (ops.hip().es_classic_episode, "es_classic_episode")
+        ops.check(fn(
+            state, state2, env._steps.data_ptr(), self.alive.data_ptr(),
+            self.member_steps.data_ptr(), self.rew_total.data_ptr(),
+            self.cl_ob_sum.data_ptr(), self.cl_ob_sumsq.data_ptr(),
+            self.weights.data_ptr(), self.obmean.data_ptr(), self.obstd.data_ptr(),
+            self.dims_arr.ctypes.data, len(self.dims_arr), self.row_stride,
+            float(self.policy._module.ob_clip), self.acstd_dev.data_ptr(),
+            self.seed_dev.data_ptr(), 0, self._classic_kind, env.ob_dim,
+            int(env.MAX_STEPS), self.B, self.max_steps, self.eps, 1,
+            (self.M - 1) * self.eps, self._stream()), name)
+        self.behv.copy_(env.positions)
+
     # ------------------------------------------------------------- rollout
     def _step_body(self, t: int):
         a = self._forward(self.obs_buf, salt=t + 1)
@@ -569,6 +629,9 @@ class GpuEngine:
         self.obs_buf.copy_(ob)
 
     def _rollout_body(self):
+        if self.classic_fused:
+            self._classic_episode()
+            return
         if self.fused and self.rollout_mode == "episode":
             # whole generation in one (+1 side) launch: every block runs its
             # member's full episode, blocks drift freely (no per-step
@@ -610,7 +673,8 @@ class GpuEngine:
 
     def _rollout(self):
         body = self._loco_step if self.fused else self._step_body
-        if self.use_graph:
+        # classic_fused: one launch, nothing for a hipGraph to save
+        if self.use_graph and not self.classic_fused:
             if self._graph is None:
                 # warmup (lazy inits must happen outside capture), then capture once
                 s = torch.cuda.Stream(self.device)
@@ -650,6 +714,9 @@ class GpuEngine:
         if self.fused:
             self.mo_sum.zero_()
             self.mo_sumsq.zero_()
+        if self.classic_fused:
+            self.cl_ob_sum.zero_()
+            self.cl_ob_sumsq.zero_()
 
     def _gen_seed(self) -> int:
         # distinct env variations per generation, identical across ranks only
@@ -722,8 +789,11 @@ class GpuEngine:
             # generic torch path computes the whole batch; only the noiseless
             # slots are read out (init-time only, cost irrelevant)
             self.weights.copy_(self.weights[self.M - 1:].expand_as(self.weights))
-            for t in range(self.max_steps):
-                self._step_body(t)
+            if self.classic_fused:
+                self._classic_episode()
+            else:
+                for t in range(self.max_steps):
+                    self._step_body(t)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         rew = float(self._member_rewards()[-1].item())
@@ -845,6 +915,13 @@ class GpuEngine:
             ob_sumsq = (self.mo_sumsq * sm).sum(0).double().cpu().numpy()
             ob_count = float((self.member_steps * self.save_mask).sum().item())
             gen_obstat.inc(ob_sum, ob_sumsq, ob_count)
+        elif self.classic_fused:
+            # the generic path's semantics: save_mask-weighted sums over the
+            # live steps, from the kernel's per-slot fp64 moments
+            sm = self.save_mask.double().unsqueeze(1)
+            gen_obstat.inc((self.cl_ob_sum * sm).sum(0).cpu().numpy(),
+                           (self.cl_ob_sumsq * sm).sum(0).cpu().numpy(),
+                           float((self.member_steps * self.save_mask).sum().item()))
         else:
             gen_obstat.inc(self.ob_sum.cpu().numpy(), self.ob_sumsq.cpu().numpy(),
                            float(self.ob_count.item()))

@@ -222,6 +222,18 @@ def _bind_hip(lib):
                                        p, i32, p, i32, i64, i64, f32, f32, p, p, p, u64,
                                        i32, i32, i32, i32, i32, i32, p]
         lib.es_tag_episode.restype = i32
+    # (state, state2, env_steps, alive, member_steps, rew_total, ob_sum,
+    # ob_sumsq; weights, obmean, obstd, dims + ndims, row_stride, ob_clip,
+    # ac_std_dev, seed_dev, salt_base; env_kind, ob_dim, env_max_steps,
+    # n_slots, n_steps, eps, act_final, noiseless_from, stream)
+    # (absent from a library of an earlier revision loaded through ES_HIP_SO)
+    if hasattr(lib, "es_classic_episode"):
+        lib.es_classic_episode.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, i32, i64,
+                                           f32, p, p, u64, i32, i32, i32, i32, i32, i32,
+                                           i32, i32, p]
+        lib.es_classic_episode.restype = i32
+        lib.es_classic_episode_f32.argtypes = lib.es_classic_episode.argtypes
+        lib.es_classic_episode_f32.restype = i32
     # fp32-weights entry points: the argument lists of their bf16 counterparts
     lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
     lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes
