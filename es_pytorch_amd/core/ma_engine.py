@@ -24,6 +24,14 @@ whole rollout of a generation in ONE launch of the fused tag kernel
 (``rollout_tag.hip``): both policies' forwards, the env step and the
 bookkeeping per game, with games that end leaving early. It draws the same
 action noise as the step loop and needs the ``BatchedPursuitTag`` env on a GPU.
+
+Two weight dtypes, for both policies alike (``weights_dtype=`` or
+``general.weights_dtype``, the single-policy engine's key). ``"bf16"`` (the
+default) evaluates the members on bf16 rows. ``"fp32"`` materializes
+``float32(theta + s*eps)`` rows (``es_pheno_f32``) and runs the fp32-weight
+forward in either rollout mode (``es_mlp_fwd_f32`` per step,
+``es_tag_episode_f32`` per episode): the reference's numerics, and what ties
+a generation to ``theta`` and the noise table in the oracle tests.
 """
 from __future__ import annotations
 
@@ -47,7 +55,8 @@ from es_pytorch_amd.utils.rankers import Ranker
 class _PolicyState:
     """Per-policy device state (theta, moments, member weight blobs)."""
 
-    def __init__(self, policy: Policy, device, pairs: int, ob_dim: int):
+    def __init__(self, policy: Policy, device, pairs: int, ob_dim: int,
+                 weights_dtype: torch.dtype = torch.bfloat16):
         self.policy = policy
         d = device
         self.dims = policy._module.layer_dims()
@@ -60,7 +69,7 @@ class _PolicyState:
         self.v = torch.zeros(self.n, dtype=torch.float32, device=d)
         self.row_stride = (self.n + 7) // 8 * 8
         M = 2 * pairs + 1
-        self.weights = torch.empty((M, self.row_stride), dtype=torch.bfloat16, device=d)
+        self.weights = torch.empty((M, self.row_stride), dtype=weights_dtype, device=d)
         self.offsets = torch.zeros(M, dtype=torch.int64, device=d)
         self.signs = torch.cat([torch.ones(pairs), -torch.ones(pairs),
                                 torch.zeros(1)]).to(d)
@@ -86,7 +95,8 @@ class _PolicyState:
 
 class MultiAgentGpuEngine:
     def __init__(self, cfg, comm: Comm, policies: List[Policy], nt: NoiseTable, env,
-                 rs: np.random.RandomState, rollout_mode: Optional[str] = None):
+                 rs: np.random.RandomState, rollout_mode: Optional[str] = None,
+                 weights_dtype: Optional[str] = None):
         self.cfg = cfg
         self.comm = comm
         self.nt = nt
@@ -113,6 +123,20 @@ class MultiAgentGpuEngine:
                     f"on a GPU, got {self.device.type!r} and {env.device.type!r} - "
                     f"use ma_rollout_mode='step'")
         self.rollout_mode = rollout_mode
+        if weights_dtype is None:
+            weights_dtype = cfg.general.get("weights_dtype", "bf16")
+        if weights_dtype not in ("bf16", "fp32"):
+            raise ValueError(f"weights_dtype must be 'bf16' or 'fp32', got "
+                             f"{weights_dtype!r}")
+        self.weights_dtype = weights_dtype
+        self.fp32 = weights_dtype == "fp32"
+        if self.fp32 and rollout_mode == "episode" and \
+                not hasattr(ops.hip(), "es_tag_episode_f32"):
+            raise RuntimeError(
+                "weights_dtype='fp32' with ma_rollout_mode='episode' needs "
+                "es_tag_episode_f32, which the loaded HIP library does not have "
+                "(an earlier revision's library?) - use ma_rollout_mode='step' or "
+                "rebuild the library")
 
         ppg = cfg.general.policies_per_gen
         assert ppg % comm.size == 0 and (ppg / comm.size) % 2 == 0
@@ -120,7 +144,8 @@ class MultiAgentGpuEngine:
         self.B = 2 * self.pairs + 1
         assert env.batch == self.B, f"env batch {env.batch} != {self.B}"
 
-        self.states = [_PolicyState(p, self.device, self.pairs, env.ob_dims[i])
+        wdt = torch.float32 if self.fp32 else torch.bfloat16
+        self.states = [_PolicyState(p, self.device, self.pairs, env.ob_dims[i], wdt)
                        for i, p in enumerate(policies)]
         self.actions = [torch.empty((self.B, env.ac_dims[i]), dtype=torch.float32,
                                     device=self.device) for i in range(self.n_agents)]
@@ -142,16 +167,24 @@ class MultiAgentGpuEngine:
         return torch.cuda.current_stream(self.device).cuda_stream if \
             self.device.type == "cuda" else None
 
+    @property
+    def numerics(self) -> dict:
+        """What the rollout evaluates with (the keys of ``GpuEngine.numerics``)."""
+        return {"weights": self.weights_dtype, "eps_encoding": "none", "path": "tag",
+                "rollout_mode": self.rollout_mode}
+
     def _forward(self, i: int, obs: torch.Tensor, salt: int):
         st = self.states[i]
-        ops.check(ops.hip().es_mlp_fwd(
+        fn, name = (ops.hip().es_mlp_fwd_f32, "es_mlp_fwd_f32") if self.fp32 else \
+            (ops.hip().es_mlp_fwd, "es_mlp_fwd")
+        ops.check(fn(
             self.actions[i].data_ptr(), obs.contiguous().data_ptr(),
             st.weights.data_ptr(), st.obmean.data_ptr(), st.obstd.data_ptr(),
             st.dims_arr.ctypes.data, len(st.dims_arr), self.seed_dev.data_ptr(),
             salt * self.n_agents + i, self.B,
             float(st.policy._module.ob_clip), st.acstd_dev.data_ptr(),
             st.row_stride, 1, self.B - 1, 0, 1, 0, None, None,
-            self._stream()), "es_mlp_fwd")
+            self._stream()), name)
         return self.actions[i]
 
     def _rollout_episode(self):
@@ -161,7 +194,9 @@ class MultiAgentGpuEngine:
         assert env.p.is_contiguous() and env.v.is_contiguous()
         self.ep_ob_sum.zero_()
         self.ep_ob_sumsq.zero_()
-        ops.check(ops.hip().es_tag_episode(
+        fn, name = (ops.hip().es_tag_episode_f32, "es_tag_episode_f32") if self.fp32 \
+            else (ops.hip().es_tag_episode, "es_tag_episode")
+        ops.check(fn(
             env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
             self.member_steps.data_ptr(), self.rew_total.data_ptr(),
             self.ep_ob_sum.data_ptr(), self.ep_ob_sumsq.data_ptr(),
@@ -172,7 +207,7 @@ class MultiAgentGpuEngine:
             float(s0.policy._module.ob_clip), float(s1.policy._module.ob_clip),
             s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(), self.seed_dev.data_ptr(),
             0, self.n_agents, env.ob_dims[0], self.B, self.max_steps, 1, self.B - 1,
-            self._stream()), "es_tag_episode")
+            self._stream()), name)
         ob_sums = [self.ep_ob_sum[:, i].sum(0) for i in range(self.n_agents)]
         ob_sumsqs = [self.ep_ob_sumsq[:, i].sum(0) for i in range(self.n_agents)]
         return ob_sums, ob_sumsqs, self.member_steps.sum().double()
@@ -186,10 +221,12 @@ class MultiAgentGpuEngine:
             st.offsets[:self.pairs].copy_(torch.from_numpy(offs).to(self.device))
             st.offsets[self.pairs:2 * self.pairs].copy_(st.offsets[:self.pairs])
             st.acstd_dev.fill_(float(getattr(st.policy._module, "_action_std", 0.0)))
-            ops.check(ops.hip().es_pheno_bf16(
+            fn, name = (ops.hip().es_pheno_f32, "es_pheno_f32") if self.fp32 else \
+                (ops.hip().es_pheno_bf16, "es_pheno_bf16")
+            ops.check(fn(
                 st.weights.data_ptr(), st.theta.data_ptr(), self.nt.noise.data_ptr(),
                 st.offsets.data_ptr(), st.signs.data_ptr(), self.B, st.n,
-                st.row_stride, float(st.policy.std), self._stream()), "es_pheno_bf16")
+                st.row_stride, float(st.policy.std), self._stream()), name)
         self.seed_dev.fill_(int(self.rs.randint(0, 2 ** 31)))
 
         self.alive.fill_(1.0)

@@ -222,6 +222,11 @@ def _bind_hip(lib):
                                        p, i32, p, i32, i64, i64, f32, f32, p, p, p, u64,
                                        i32, i32, i32, i32, i32, i32, p]
         lib.es_tag_episode.restype = i32
+    # fp32 member rows, same argument list (a guard of its own: a library may
+    # have es_tag_episode without it)
+    if hasattr(lib, "es_tag_episode_f32"):
+        lib.es_tag_episode_f32.argtypes = lib.es_tag_episode.argtypes
+        lib.es_tag_episode_f32.restype = i32
     # (state, state2, env_steps, alive, member_steps, rew_total, ob_sum,
     # ob_sumsq; weights, obmean, obstd, dims + ndims, row_stride, ob_clip,
     # ac_std_dev, seed_dev, salt_base; env_kind, ob_dim, env_max_steps,

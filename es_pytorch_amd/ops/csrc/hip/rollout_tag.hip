@@ -2,9 +2,11 @@
 // (envs/multiagent.py, BatchedPursuitTag) for the co-evolution engine.
 //
 // One 256-thread workgroup per game b plays up to n_steps env steps in one
-// launch: per step it runs agent 0's and agent 1's MLP (mlp_layers, each on
-// member row b of that policy's own bf16 blob), steps the game and does the
-// engine's bookkeeping (reward and step totals, fp64 observation moments).
+// launch: per step it runs agent 0's and agent 1's MLP (each on member row b
+// of that policy's own blob: mlp_layers on bf16 rows, mlp_layers_f32 on fp32
+// rows, one kernel body templated on the weight element type), steps the game
+// and does the engine's bookkeeping (reward and step totals, fp64 observation
+// moments).
 // The game state lives in LDS between steps; it is read from global memory at
 // launch and written back at the end, so a rollout may be cut into several
 // launches with salt_base continuing. A game that ends leaves the step loop:
@@ -22,7 +24,7 @@
 #define TAG_SLAB_BYTES (2 * 2 * TAG_OB * 8 + 16 * 4)
 
 struct TagPolicy {
-  const uint16_t* weights;
+  const void* weights;  // member rows of the kernel's weight type, row_stride apart
   const float* obmean;
   const float* obstd;
   const float* ac_std_dev;
@@ -33,6 +35,7 @@ struct TagPolicy {
 
 // Agent i's forward on the pre-step state: writes its two raw actions to
 // act[2i], act[2i+1]. Ends on a barrier, so bufA/bufB are free afterwards.
+template <typename WT>
 __device__ __forceinline__ void tag_agent_forward(
     const TagPolicy& P, int i, int b, const float* st, float* act, float* bufA,
     float* bufB, float* partial, float mean_k, float std_k, uint64_t seed,
@@ -44,8 +47,12 @@ __device__ __forceinline__ void tag_agent_forward(
     bufA[tid] = fclampf((ob - mean_k) / std_k, -P.ob_clip, P.ob_clip);
   }
   __syncthreads();
-  const float* out = mlp_layers(P.weights + (int64_t)b * P.row_stride, P.sh, bufA, bufB,
-                                partial, tid, 256, act_final);
+  const WT* wb = reinterpret_cast<const WT*>(P.weights) + (int64_t)b * P.row_stride;
+  const float* out;
+  if constexpr (sizeof(WT) == 4)
+    out = mlp_layers_f32(wb, P.sh, bufA, bufB, partial, tid, 256, act_final);
+  else
+    out = mlp_layers(wb, P.sh, bufA, bufB, partial, tid, 256, act_final);
   if (tid < TAG_AC) {
     const int A = P.sh.dims[P.sh.n_layers];
     const float ac_std = P.ac_std_dev ? *P.ac_std_dev : 0.0f;
@@ -57,6 +64,7 @@ __device__ __forceinline__ void tag_agent_forward(
   __syncthreads();
 }
 
+template <typename WT>
 __global__ void __launch_bounds__(256)
 tag_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
                    float* __restrict__ alive_g, float* __restrict__ steps_g,
@@ -102,10 +110,10 @@ tag_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
   for (int t = 0; t < n_steps && alive; ++t) {
     // the key of es_mlp_fwd at salt (t+1)*2 + i: the per-step engine's draw
     const uint64_t seed = seed0 + (salt_base + (uint64_t)t + 1) * 2;
-    tag_agent_forward(P0, 0, b, st, act, bufA, bufB, partial, mean0, std0, seed,
-                      act_final, noiseless_from, tid);
-    tag_agent_forward(P1, 1, b, st, act, bufA, bufB, partial, mean1, std1, seed + 1,
-                      act_final, noiseless_from, tid);
+    tag_agent_forward<WT>(P0, 0, b, st, act, bufA, bufB, partial, mean0, std0, seed,
+                          act_final, noiseless_from, tid);
+    tag_agent_forward<WT>(P1, 1, b, st, act, bufA, bufB, partial, mean1, std1, seed + 1,
+                          act_final, noiseless_from, tid);
     {
       // BatchedPursuitTag.step, op for op in fp32
 #pragma clang fp contract(off)
@@ -155,20 +163,55 @@ tag_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
   }
 }
 
-static inline int tag_policy_init(TagPolicy* P, const void* weights, const void* obmean,
-                                  const void* obstd, const void* ac_std_dev,
-                                  const int32_t* dims_host, int32_t ndims,
-                                  int64_t row_stride, float ob_clip) {
+// f32: the rows are float32 and a layer is quad-tiled only where its 16-B
+// loads are aligned for THIS policy's stride (mlp_shape_vec_f32).
+static inline int tag_policy_init(TagPolicy* P, bool f32, const void* weights,
+                                  const void* obmean, const void* obstd,
+                                  const void* ac_std_dev, const int32_t* dims_host,
+                                  int32_t ndims, int64_t row_stride, float ob_clip) {
   int rc = mlp_shape_init(&P->sh, dims_host, ndims, row_stride);
   if (rc) return rc;
+  if (f32) mlp_shape_vec_f32(&P->sh, row_stride);
   if (P->sh.dims[0] != TAG_OB) return -110;
   if (P->sh.dims[P->sh.n_layers] < TAG_AC) return -111;
-  P->weights = (const uint16_t*)weights;
+  P->weights = weights;
   P->obmean = (const float*)obmean;
   P->obstd = (const float*)obstd;
   P->ac_std_dev = (const float*)ac_std_dev;
   P->row_stride = row_stride;
   P->ob_clip = ob_clip;
+  return 0;
+}
+
+static inline int tag_launch(bool f32, void* p, void* v, void* alive, void* steps,
+                             void* rew_total, void* ob_sum, void* ob_sumsq,
+                             const void* weights0, const void* weights1,
+                             const void* obmean0, const void* obmean1, const void* obstd0,
+                             const void* obstd1, const int32_t* dims0_host, int32_t ndims0,
+                             const int32_t* dims1_host, int32_t ndims1, int64_t row_stride0,
+                             int64_t row_stride1, float ob_clip0, float ob_clip1,
+                             const void* ac_std_dev0, const void* ac_std_dev1,
+                             const void* seed_dev, uint64_t salt_base, int32_t n_agents,
+                             int32_t ob_dim, int32_t n_games, int32_t n_steps,
+                             int32_t act_final, int32_t noiseless_from, void* stream) {
+  if (n_agents != 2) return -112;
+  if (ob_dim != TAG_OB) return -110;
+  TagPolicy P0, P1;
+  int rc = tag_policy_init(&P0, f32, weights0, obmean0, obstd0, ac_std_dev0, dims0_host,
+                           ndims0, row_stride0, ob_clip0);
+  if (rc) return rc;
+  rc = tag_policy_init(&P1, f32, weights1, obmean1, obstd1, ac_std_dev1, dims1_host, ndims1,
+                       row_stride1, ob_clip1);
+  if (rc) return rc;
+  if (n_games <= 0 || n_steps <= 0) return 0;
+  const int maxdim = std::max(P0.sh.maxdim, P1.sh.maxdim);
+  const unsigned lds = (unsigned)(mlp_lds_bytes(maxdim) + TAG_SLAB_BYTES);
+  auto kernel = f32 ? tag_episode_kernel<float> : tag_episode_kernel<uint16_t>;
+  kernel<<<dim3((unsigned)n_games), dim3(256), lds, (hipStream_t)stream>>>(
+      (float*)p, (float*)v, (float*)alive, (float*)steps, (float*)rew_total,
+      (double*)ob_sum, (double*)ob_sumsq, P0, P1, maxdim, (const uint64_t*)seed_dev,
+      salt_base, n_steps, act_final, noiseless_from);
+  ES_CHECK_LAUNCH();
   return 0;
 }
 
@@ -191,22 +234,34 @@ extern "C" int es_tag_episode(void* p, void* v, void* alive, void* steps, void* 
                               uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
                               int32_t n_games, int32_t n_steps, int32_t act_final,
                               int32_t noiseless_from, void* stream) {
-  if (n_agents != 2) return -112;
-  if (ob_dim != TAG_OB) return -110;
-  TagPolicy P0, P1;
-  int rc = tag_policy_init(&P0, weights0, obmean0, obstd0, ac_std_dev0, dims0_host, ndims0,
-                           row_stride0, ob_clip0);
-  if (rc) return rc;
-  rc = tag_policy_init(&P1, weights1, obmean1, obstd1, ac_std_dev1, dims1_host, ndims1,
-                       row_stride1, ob_clip1);
-  if (rc) return rc;
-  if (n_games <= 0 || n_steps <= 0) return 0;
-  const int maxdim = std::max(P0.sh.maxdim, P1.sh.maxdim);
-  const unsigned lds = (unsigned)(mlp_lds_bytes(maxdim) + TAG_SLAB_BYTES);
-  tag_episode_kernel<<<dim3((unsigned)n_games), dim3(256), lds, (hipStream_t)stream>>>(
-      (float*)p, (float*)v, (float*)alive, (float*)steps, (float*)rew_total,
-      (double*)ob_sum, (double*)ob_sumsq, P0, P1, maxdim, (const uint64_t*)seed_dev,
-      salt_base, n_steps, act_final, noiseless_from);
-  ES_CHECK_LAUNCH();
-  return 0;
+  return tag_launch(false, p, v, alive, steps, rew_total, ob_sum, ob_sumsq, weights0,
+                    weights1, obmean0, obmean1, obstd0, obstd1, dims0_host, ndims0,
+                    dims1_host, ndims1, row_stride0, row_stride1, ob_clip0, ob_clip1,
+                    ac_std_dev0, ac_std_dev1, seed_dev, salt_base, n_agents, ob_dim, n_games,
+                    n_steps, act_final, noiseless_from, stream);
+}
+
+// fp32 rows: same argument list and return codes; weights_i is float32
+// (n_games, row_stride_i), row_stride_i counted in floats. A policy whose
+// stride is no multiple of 4 floats, and any layer whose weight block is not
+// 16-B aligned in the row or whose width is no multiple of 4, takes the
+// scalar walks.
+extern "C" int es_tag_episode_f32(void* p, void* v, void* alive, void* steps,
+                                  void* rew_total, void* ob_sum, void* ob_sumsq,
+                                  const void* weights0, const void* weights1,
+                                  const void* obmean0, const void* obmean1,
+                                  const void* obstd0, const void* obstd1,
+                                  const int32_t* dims0_host, int32_t ndims0,
+                                  const int32_t* dims1_host, int32_t ndims1,
+                                  int64_t row_stride0, int64_t row_stride1, float ob_clip0,
+                                  float ob_clip1, const void* ac_std_dev0,
+                                  const void* ac_std_dev1, const void* seed_dev,
+                                  uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
+                                  int32_t n_games, int32_t n_steps, int32_t act_final,
+                                  int32_t noiseless_from, void* stream) {
+  return tag_launch(true, p, v, alive, steps, rew_total, ob_sum, ob_sumsq, weights0,
+                    weights1, obmean0, obmean1, obstd0, obstd1, dims0_host, ndims0,
+                    dims1_host, ndims1, row_stride0, row_stride1, ob_clip0, ob_clip1,
+                    ac_std_dev0, ac_std_dev1, seed_dev, salt_base, n_agents, ob_dim, n_games,
+                    n_steps, act_final, noiseless_from, stream);
 }

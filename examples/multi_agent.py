@@ -136,9 +136,12 @@ def main_gpu(cfg, comm, rs):
                                   reporter, cfg.general.seed, device=comm.device)
     # general.ma_rollout_mode: "step" (default) or "episode", the fused
     # whole-episode kernel (configs/multi_agent_fused.json)
+    # general.weights_dtype: "bf16" (default) or "fp32" member rows
+    # (configs/multi_agent_fp32.json)
     engine = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs,
-                                 rollout_mode=cfg.general.get("ma_rollout_mode"))
-    reporter.print(f"rollout mode: {engine.rollout_mode}")
+                                 rollout_mode=cfg.general.get("ma_rollout_mode"),
+                                 weights_dtype=cfg.general.get("weights_dtype"))
+    reporter.print(f"rollout mode: {engine.rollout_mode}, numerics: {engine.numerics}")
     for gen in range(cfg.general.gens):
         reporter.start_gen()
         rankers = [CenteredRanker() for _ in range(env.N_AGENTS)]

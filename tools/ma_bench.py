@@ -7,7 +7,9 @@ For every grid point two engines are built from the same seeds, one per mode,
 and their generations ALTERNATE (step, episode, step, ...) after a warm-up,
 so both see the same machine state. Each generation ends in a device
 synchronise inside engine.step; rollout_s and gen_s are the engine's own
-timings. Games that end stop early in episode mode, so the mean episode
+timings. --weights-dtype bf16 fp32 adds the member-row dtype as another
+alternating axis (one engine per mode and dtype). Games that end stop early
+in episode mode, so the mean episode
 length is printed with every row: it is part of the answer.
 
 The project's bar for a speed claim: the SLOWEST run of the new mode must
@@ -28,7 +30,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
-def make_engine(dev, mode, ppg, layers, max_steps, seed):
+def make_engine(dev, mode, ppg, layers, max_steps, seed, wdtype="bf16"):
     from es_pytorch_amd.config import AttrDict
     from es_pytorch_amd.core.ma_engine import MultiAgentGpuEngine
     from es_pytorch_amd.core.noisetable import NoiseTable
@@ -61,8 +63,12 @@ def make_engine(dev, mode, ppg, layers, max_steps, seed):
     # "step" is the constructor's default: built without the keyword, so the
     # same script times a revision from before the keyword existed
     kw = {} if mode == "step" else {"rollout_mode": mode}
+    # likewise "bf16": a revision from before weights_dtype ran bf16 rows
+    if wdtype != "bf16":
+        kw["weights_dtype"] = wdtype
     eng = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs, **kw)
     assert getattr(eng, "rollout_mode", "step") == mode
+    assert getattr(eng, "weights_dtype", "bf16") == wdtype
     return eng
 
 
@@ -79,6 +85,8 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("--modes", nargs="+", default=["step", "episode"],
                    choices=["step", "episode"])
+    p.add_argument("--weights-dtype", nargs="+", default=["bf16"],
+                   choices=["bf16", "fp32"], help="member-row dtypes to alternate")
     p.add_argument("--ppg", type=int, nargs="+", default=[32, 1024, 4096])
     p.add_argument("--nets", nargs="+", default=["32,32", "256,256"],
                    help="hidden layer sizes, comma separated, one net per item")
@@ -93,39 +101,45 @@ def main():
     dev = torch.device("cuda", 0)
 
     rows = []
-    print(f"{'ppg':>5} {'net':>9} {'mode':>8} {'rollout_s med':>13} {'min':>9} {'max':>9} "
-          f"{'gen_s med':>10} {'env-steps/s':>12} {'ep_len':>7}")
+    variants = [(m, w) for m in args.modes for w in args.weights_dtype]
+    print(f"{'ppg':>5} {'net':>9} {'mode':>8} {'dtype':>5} {'rollout_s med':>13} {'min':>9} "
+          f"{'max':>9} {'gen_s med':>10} {'env-steps/s':>12} {'ep_len':>7}")
     for ppg in args.ppg:
         for net in args.nets:
             layers = [int(x) for x in net.split(",")]
-            engs = {m: make_engine(dev, m, ppg, layers, args.max_steps, args.seed)
-                    for m in args.modes}
-            runs = {m: [] for m in args.modes}
+            engs = {k: make_engine(dev, k[0], ppg, layers, args.max_steps, args.seed, k[1])
+                    for k in variants}
+            runs = {k: [] for k in variants}
             for g in range(args.warmup + args.gens):
-                for m in args.modes:            # alternate the modes
-                    t = one_gen(engs[m])
+                for k in variants:              # alternate the modes and dtypes
+                    t = one_gen(engs[k])
                     if g >= args.warmup:
-                        runs[m].append(t)
+                        runs[k].append(t)
             point = {}
-            for m in args.modes:
-                ro = np.array([t["rollout_s"] for t in runs[m]])
-                row = {"ppg": ppg, "net": layers, "mode": m, "max_steps": args.max_steps,
+            for k in variants:
+                m, w = k
+                ro = np.array([t["rollout_s"] for t in runs[k]])
+                row = {"ppg": ppg, "net": layers, "mode": m, "weights_dtype": w,
+                       "max_steps": args.max_steps,
                        "rollout_s": ro.tolist(),
                        "rollout_s_med": float(np.median(ro)),
-                       "gen_s_med": float(np.median([t["gen_s"] for t in runs[m]])),
+                       "gen_s_med": float(np.median([t["gen_s"] for t in runs[k]])),
                        "env_steps_per_s": float(np.median(
-                           [t["env_steps"] / t["rollout_s"] for t in runs[m]])),
-                       "ep_len": float(np.mean([t["ep_len"] for t in runs[m]]))}
-                point[m] = row
+                           [t["env_steps"] / t["rollout_s"] for t in runs[k]])),
+                       "ep_len": float(np.mean([t["ep_len"] for t in runs[k]]))}
+                point[k] = row
                 rows.append(row)
-                print(f"{ppg:>5} {net:>9} {m:>8} {row['rollout_s_med']:>13.5f} "
+                print(f"{ppg:>5} {net:>9} {m:>8} {w:>5} {row['rollout_s_med']:>13.5f} "
                       f"{ro.min():>9.5f} {ro.max():>9.5f} {row['gen_s_med']:>10.5f} "
                       f"{row['env_steps_per_s']:>12.4g} {row['ep_len']:>7.1f}", flush=True)
-            if len(point) == 2:
-                s, e = (np.array(point[m]["rollout_s"]) for m in ("step", "episode"))
+            for w in args.weights_dtype:
+                if not all((m, w) in point for m in ("step", "episode")):
+                    continue
+                s, e = (np.array(point[m, w]["rollout_s"]) for m in ("step", "episode"))
                 spread = max(s.max() - s.min(), e.max() - e.min())
                 lead = s.min() - e.max()
-                verdict = {"ppg": ppg, "net": layers, "lead_s": float(lead),
+                verdict = {"ppg": ppg, "net": layers, "weights_dtype": w,
+                           "lead_s": float(lead),
                            "spread_s": float(spread), "clears_bar": bool(lead >= 3 * spread),
                            "speedup_med": float(np.median(s) / np.median(e))}
                 rows.append(verdict)
@@ -133,6 +147,12 @@ def main():
                       f"{spread:.5f} s, bar (3x spread) "
                       f"{'cleared' if verdict['clears_bar'] else 'NOT cleared'}, "
                       f"median rollout speed-up {verdict['speedup_med']:.1f}x", flush=True)
+            for m in args.modes:
+                if (m, "bf16") in point and (m, "fp32") in point:
+                    r = point[m, "fp32"]["rollout_s_med"] / point[m, "bf16"]["rollout_s_med"]
+                    rows.append({"ppg": ppg, "net": layers, "mode": m,
+                                 "fp32_over_bf16_rollout_med": float(r)})
+                    print(f"      {m}: fp32 / bf16 median rollout_s = {r:.2f}", flush=True)
             del engs
             torch.cuda.empty_cache()
     if args.json:
