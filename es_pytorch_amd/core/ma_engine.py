@@ -32,6 +32,14 @@ default) evaluates the members on bf16 rows. ``"fp32"`` materializes
 forward in either rollout mode (``es_mlp_fwd_f32`` per step,
 ``es_tag_episode_f32`` per episode): the reference's numerics, and what ties
 a generation to ``theta`` and the noise table in the oracle tests.
+
+``pair_rollout=True`` (or ``general.ma_pair_rollout``; bf16, episode mode
+only) shares the rows across the two games of an antithetic pair: no member
+blob is materialized, one workgroup of ``es_tag_pair_episode`` plays games p
+and pairs + p on ``bf16(theta) +- bf16(sigma*eps_p)``, streaming ONE
+sigma*eps row per policy plus the theta row the whole grid shares. Two bf16
+roundings instead of one; the gradient uses the unquantized noise, as on the
+single-policy bf16 pair path. Off by default.
 """
 from __future__ import annotations
 
@@ -56,7 +64,7 @@ class _PolicyState:
     """Per-policy device state (theta, moments, member weight blobs)."""
 
     def __init__(self, policy: Policy, device, pairs: int, ob_dim: int,
-                 weights_dtype: torch.dtype = torch.bfloat16):
+                 weights_dtype: torch.dtype = torch.bfloat16, pair: bool = False):
         self.policy = policy
         d = device
         self.dims = policy._module.layer_dims()
@@ -69,7 +77,23 @@ class _PolicyState:
         self.v = torch.zeros(self.n, dtype=torch.float32, device=d)
         self.row_stride = (self.n + 7) // 8 * 8
         M = 2 * pairs + 1
-        self.weights = torch.empty((M, self.row_stride), dtype=weights_dtype, device=d)
+        if pair:
+            # no member blob: one theta row and `pairs` sigma*eps rows, the
+            # row behind them zero for the noiseless block; one guard row
+            # each, as the single-policy engine keeps for the pair forward
+            self._theta_blob = torch.zeros((2, self.row_stride), dtype=torch.bfloat16,
+                                           device=d)
+            self.theta_row = self._theta_blob[:1]
+            self._eps_blob = torch.zeros((pairs + 2, self.row_stride),
+                                         dtype=torch.bfloat16, device=d)
+            self.eps_rows = self._eps_blob[:pairs]
+            self._zeros_n = torch.zeros(self.n, dtype=torch.float32, device=d)
+            self._zero_off = torch.zeros(1, dtype=torch.int64, device=d)
+            self._zero_sign = torch.zeros(1, dtype=torch.float32, device=d)
+            self._one_signs = torch.ones(pairs, dtype=torch.float32, device=d)
+        else:
+            self.weights = torch.empty((M, self.row_stride), dtype=weights_dtype,
+                                       device=d)
         self.offsets = torch.zeros(M, dtype=torch.int64, device=d)
         self.signs = torch.cat([torch.ones(pairs), -torch.ones(pairs),
                                 torch.zeros(1)]).to(d)
@@ -96,7 +120,8 @@ class _PolicyState:
 class MultiAgentGpuEngine:
     def __init__(self, cfg, comm: Comm, policies: List[Policy], nt: NoiseTable, env,
                  rs: np.random.RandomState, rollout_mode: Optional[str] = None,
-                 weights_dtype: Optional[str] = None):
+                 weights_dtype: Optional[str] = None,
+                 pair_rollout: Optional[bool] = None):
         self.cfg = cfg
         self.comm = comm
         self.nt = nt
@@ -137,6 +162,29 @@ class MultiAgentGpuEngine:
                 "es_tag_episode_f32, which the loaded HIP library does not have "
                 "(an earlier revision's library?) - use ma_rollout_mode='step' or "
                 "rebuild the library")
+        # general.ma_pair_rollout, NOT the single-policy engine's pair_rollout:
+        # that key is size-gated and sits in most configs users copy from
+        if pair_rollout is None:
+            pair_rollout = cfg.general.get("ma_pair_rollout", False)
+        if not isinstance(pair_rollout, bool):
+            raise ValueError(f"ma_pair_rollout must be true or false, got "
+                             f"{pair_rollout!r}")
+        if pair_rollout and self.fp32:
+            raise ValueError(
+                "ma_pair_rollout evaluates bf16(theta) +- bf16(sigma*eps) and has no "
+                "fp32 form - use weights_dtype='bf16' or leave ma_pair_rollout off")
+        if pair_rollout and rollout_mode != "episode":
+            raise ValueError(
+                f"ma_pair_rollout shares the rows of an antithetic pair inside the "
+                f"fused kernel and needs ma_rollout_mode='episode', got "
+                f"{rollout_mode!r} - set ma_rollout_mode='episode' or leave "
+                f"ma_pair_rollout off")
+        if pair_rollout and not hasattr(ops.hip(), "es_tag_pair_episode"):
+            raise RuntimeError(
+                "ma_pair_rollout needs es_tag_pair_episode, which the loaded HIP "
+                "library does not have (an earlier revision's library?) - leave "
+                "ma_pair_rollout off or rebuild the library")
+        self.pair_rollout = pair_rollout
 
         ppg = cfg.general.policies_per_gen
         assert ppg % comm.size == 0 and (ppg / comm.size) % 2 == 0
@@ -145,7 +193,8 @@ class MultiAgentGpuEngine:
         assert env.batch == self.B, f"env batch {env.batch} != {self.B}"
 
         wdt = torch.float32 if self.fp32 else torch.bfloat16
-        self.states = [_PolicyState(p, self.device, self.pairs, env.ob_dims[i], wdt)
+        self.states = [_PolicyState(p, self.device, self.pairs, env.ob_dims[i], wdt,
+                                    pair=self.pair_rollout)
                        for i, p in enumerate(policies)]
         self.actions = [torch.empty((self.B, env.ac_dims[i]), dtype=torch.float32,
                                     device=self.device) for i in range(self.n_agents)]
@@ -170,6 +219,9 @@ class MultiAgentGpuEngine:
     @property
     def numerics(self) -> dict:
         """What the rollout evaluates with (the keys of ``GpuEngine.numerics``)."""
+        if self.pair_rollout:
+            return {"weights": "bf16", "eps_encoding": "bf16", "path": "tag_pair",
+                    "rollout_mode": "episode"}
         return {"weights": self.weights_dtype, "eps_encoding": "none", "path": "tag",
                 "rollout_mode": self.rollout_mode}
 
@@ -194,6 +246,21 @@ class MultiAgentGpuEngine:
         assert env.p.is_contiguous() and env.v.is_contiguous()
         self.ep_ob_sum.zero_()
         self.ep_ob_sumsq.zero_()
+        if self.pair_rollout:
+            ops.check(ops.hip().es_tag_pair_episode(
+                env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
+                self.member_steps.data_ptr(), self.rew_total.data_ptr(),
+                self.ep_ob_sum.data_ptr(), self.ep_ob_sumsq.data_ptr(),
+                s0.theta_row.data_ptr(), s1.theta_row.data_ptr(),
+                s0.eps_rows.data_ptr(), s1.eps_rows.data_ptr(), s0.obmean.data_ptr(),
+                s1.obmean.data_ptr(), s0.obstd.data_ptr(), s1.obstd.data_ptr(),
+                s0.dims_arr.ctypes.data, len(s0.dims_arr), s1.dims_arr.ctypes.data,
+                len(s1.dims_arr), s0.row_stride, s1.row_stride,
+                float(s0.policy._module.ob_clip), float(s1.policy._module.ob_clip),
+                s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(),
+                self.seed_dev.data_ptr(), 0, self.n_agents, env.ob_dims[0], self.pairs, 1,
+                self.max_steps, 1, self.B - 1, self._stream()), "es_tag_pair_episode")
+            return self._episode_sums()
         fn, name = (ops.hip().es_tag_episode_f32, "es_tag_episode_f32") if self.fp32 \
             else (ops.hip().es_tag_episode, "es_tag_episode")
         ops.check(fn(
@@ -208,9 +275,25 @@ class MultiAgentGpuEngine:
             s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(), self.seed_dev.data_ptr(),
             0, self.n_agents, env.ob_dims[0], self.B, self.max_steps, 1, self.B - 1,
             self._stream()), name)
+        return self._episode_sums()
+
+    def _episode_sums(self):
         ob_sums = [self.ep_ob_sum[:, i].sum(0) for i in range(self.n_agents)]
         ob_sumsqs = [self.ep_ob_sumsq[:, i].sum(0) for i in range(self.n_agents)]
         return ob_sums, ob_sumsqs, self.member_steps.sum().double()
+
+    def _pheno_pair(self, st: _PolicyState):
+        """GpuEngine._pheno's pair form: sign 0 gives the bf16(theta) row, zero
+        theta and sign +1 the bf16(sigma*noise[off_p:]) rows."""
+        fn = ops.hip().es_pheno_bf16
+        ops.check(fn(
+            st.theta_row.data_ptr(), st.theta.data_ptr(), self.nt.noise.data_ptr(),
+            st._zero_off.data_ptr(), st._zero_sign.data_ptr(), 1, st.n, st.row_stride,
+            0.0, self._stream()), "es_pheno_bf16")
+        ops.check(fn(
+            st.eps_rows.data_ptr(), st._zeros_n.data_ptr(), self.nt.noise.data_ptr(),
+            st.offsets.data_ptr(), st._one_signs.data_ptr(), self.pairs, st.n,
+            st.row_stride, float(st.policy.std), self._stream()), "es_pheno_bf16")
 
     def step(self, rankers: List[Ranker]) -> Tuple[List[float], List[ObStat]]:
         """One co-evolution generation; every policy updated from its own
@@ -221,6 +304,9 @@ class MultiAgentGpuEngine:
             st.offsets[:self.pairs].copy_(torch.from_numpy(offs).to(self.device))
             st.offsets[self.pairs:2 * self.pairs].copy_(st.offsets[:self.pairs])
             st.acstd_dev.fill_(float(getattr(st.policy._module, "_action_std", 0.0)))
+            if self.pair_rollout:
+                self._pheno_pair(st)
+                continue
             fn, name = (ops.hip().es_pheno_f32, "es_pheno_f32") if self.fp32 else \
                 (ops.hip().es_pheno_bf16, "es_pheno_bf16")
             ops.check(fn(

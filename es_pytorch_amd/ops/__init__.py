@@ -227,6 +227,14 @@ def _bind_hip(lib):
     if hasattr(lib, "es_tag_episode_f32"):
         lib.es_tag_episode_f32.argtypes = lib.es_tag_episode.argtypes
         lib.es_tag_episode_f32.restype = i32
+    # antithetic-pair form: (state as above; theta0, theta1, eps0, eps1 in
+    # place of the two weight blobs; then as above up to ob_dim; n_pairs,
+    # n_single, n_steps, act_final, noiseless_from, stream)
+    if hasattr(lib, "es_tag_pair_episode"):
+        lib.es_tag_pair_episode.argtypes = [p, p, p, p, p, p, p, p, p, p, p, p, p, p, p,
+                                            p, i32, p, i32, i64, i64, f32, f32, p, p, p,
+                                            u64, i32, i32, i32, i32, i32, i32, i32, p]
+        lib.es_tag_pair_episode.restype = i32
     # (state, state2, env_steps, alive, member_steps, rew_total, ob_sum,
     # ob_sumsq; weights, obmean, obstd, dims + ndims, row_stride, ob_clip,
     # ac_std_dev, seed_dev, salt_base; env_kind, ob_dim, env_max_steps,

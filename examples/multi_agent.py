@@ -138,9 +138,13 @@ def main_gpu(cfg, comm, rs):
     # whole-episode kernel (configs/multi_agent_fused.json)
     # general.weights_dtype: "bf16" (default) or "fp32" member rows
     # (configs/multi_agent_fp32.json)
+    # general.ma_pair_rollout: share the theta and sigma*eps rows across the
+    # two games of an antithetic pair (bf16, "episode" only;
+    # configs/multi_agent_pair.json)
     engine = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs,
                                  rollout_mode=cfg.general.get("ma_rollout_mode"),
-                                 weights_dtype=cfg.general.get("weights_dtype"))
+                                 weights_dtype=cfg.general.get("weights_dtype"),
+                                 pair_rollout=cfg.general.get("ma_pair_rollout"))
     reporter.print(f"rollout mode: {engine.rollout_mode}, numerics: {engine.numerics}")
     for gen in range(cfg.general.gens):
         reporter.start_gen()

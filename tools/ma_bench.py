@@ -12,12 +12,19 @@ alternating axis (one engine per mode and dtype). Games that end stop early
 in episode mode, so the mean episode
 length is printed with every row: it is part of the answer.
 
+Mode "pair" is episode mode with pair_rollout=True (es_tag_pair_episode: one
+workgroup plays both games of an antithetic pair on shared theta and
+sigma*eps rows; bf16 only). It alternates with the others and gets a verdict
+of its own against "episode": a pair block lasts as long as the longer of its
+two episodes and the grid has half as many blocks, so small points may lose.
+
 The project's bar for a speed claim: the SLOWEST run of the new mode must
 lead the FASTEST run of the old one by at least three times the run-to-run
 spread (max - min within a mode, the larger of the two).
 
   python tools/ma_bench.py                      # the whole grid, both modes
   python tools/ma_bench.py --modes step         # baseline only
+  python tools/ma_bench.py --modes episode pair # pair sharing against per-game rows
 """
 import argparse
 import json
@@ -62,12 +69,15 @@ def make_engine(dev, mode, ppg, layers, max_steps, seed, wdtype="bf16"):
     rs = np.random.RandomState(seed + 1)
     # "step" is the constructor's default: built without the keyword, so the
     # same script times a revision from before the keyword existed
-    kw = {} if mode == "step" else {"rollout_mode": mode}
+    kw = {} if mode == "step" else {"rollout_mode": "episode"}
+    if mode == "pair":
+        kw["pair_rollout"] = True
     # likewise "bf16": a revision from before weights_dtype ran bf16 rows
     if wdtype != "bf16":
         kw["weights_dtype"] = wdtype
     eng = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs, **kw)
-    assert getattr(eng, "rollout_mode", "step") == mode
+    assert getattr(eng, "rollout_mode", "step") == ("episode" if mode == "pair" else mode)
+    assert getattr(eng, "pair_rollout", False) == (mode == "pair")
     assert getattr(eng, "weights_dtype", "bf16") == wdtype
     return eng
 
@@ -84,7 +94,7 @@ def one_gen(eng):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--modes", nargs="+", default=["step", "episode"],
-                   choices=["step", "episode"])
+                   choices=["step", "episode", "pair"])
     p.add_argument("--weights-dtype", nargs="+", default=["bf16"],
                    choices=["bf16", "fp32"], help="member-row dtypes to alternate")
     p.add_argument("--ppg", type=int, nargs="+", default=[32, 1024, 4096])
@@ -101,7 +111,10 @@ def main():
     dev = torch.device("cuda", 0)
 
     rows = []
-    variants = [(m, w) for m in args.modes for w in args.weights_dtype]
+    variants = [(m, w) for m in args.modes for w in args.weights_dtype
+                if not (m == "pair" and w != "bf16")]      # pair has no fp32 form
+    if not variants:
+        sys.exit("mode pair runs bf16 rows only: add bf16 to --weights-dtype")
     print(f"{'ppg':>5} {'net':>9} {'mode':>8} {'dtype':>5} {'rollout_s med':>13} {'min':>9} "
           f"{'max':>9} {'gen_s med':>10} {'env-steps/s':>12} {'ep_len':>7}")
     for ppg in args.ppg:
@@ -147,6 +160,20 @@ def main():
                       f"{spread:.5f} s, bar (3x spread) "
                       f"{'cleared' if verdict['clears_bar'] else 'NOT cleared'}, "
                       f"median rollout speed-up {verdict['speedup_med']:.1f}x", flush=True)
+            if ("episode", "bf16") in point and ("pair", "bf16") in point:
+                e, q = (np.array(point[m, "bf16"]["rollout_s"]) for m in ("episode", "pair"))
+                spread = max(e.max() - e.min(), q.max() - q.min())
+                lead = e.min() - q.max()
+                verdict = {"ppg": ppg, "net": layers, "weights_dtype": "bf16",
+                           "pair_vs_episode": True, "lead_s": float(lead),
+                           "spread_s": float(spread), "clears_bar": bool(lead > 3 * spread),
+                           "speedup_med": float(np.median(e) / np.median(q))}
+                rows.append(verdict)
+                print(f"      fastest episode - slowest pair = {lead:.5f} s, spread "
+                      f"{spread:.5f} s, bar (3x spread) "
+                      f"{'cleared' if verdict['clears_bar'] else 'NOT cleared'}, "
+                      f"median rollout episode / pair {verdict['speedup_med']:.2f}x",
+                      flush=True)
             for m in args.modes:
                 if (m, "bf16") in point and (m, "fp32") in point:
                     r = point[m, "fp32"]["rollout_s_med"] / point[m, "bf16"]["rollout_s_med"]
