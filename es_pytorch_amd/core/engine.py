@@ -24,6 +24,8 @@ One rank = one GPU; per generation:
    (``gym_runner.py:63-64``); ``classic_fused`` (opt-in) plays CartPole and
    Pendulum rollouts in ONE whole-episode launch instead
    (``rollout_classic.hip``), ended slots leaving the kernel's loop;
+   ``classic_wave`` (opt-in, nets at most 64 wide) gives each slot a
+   wavefront instead of a workgroup (``rollout_classic_wave.hip``);
 4. (fit+, fit-, idx) fp64 triples go through ONE RCCL all_gather over xGMI
    (replaces the replicated Alltoall, ``es.py:84-95``); ranking runs
    redundantly on every rank (reference README.md:10-12 — parameters are
@@ -100,7 +102,8 @@ class GpuEngine:
                  pair_rollout: Optional[bool] = None,
                  eps_fp8: Optional[bool] = None,
                  weights_dtype: Optional[str] = None,
-                 classic_fused: Optional[bool] = None):
+                 classic_fused: Optional[bool] = None,
+                 classic_wave: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -340,11 +343,23 @@ class GpuEngine:
         # ONE launch per generation instead of max_steps x (forward + a dozen
         # torch kernels), slots whose episode ends leave the loop. Opt-in;
         # `fused` keeps meaning the locomotion path.
+        # classic_wave (opt-in, implies classic_fused): the wave-per-slot
+        # kernel for nets whose layers are all at most 64 wide
+        # (rollout_classic_wave.hip). Never chosen by size, never a fallback.
+        if classic_wave is None:
+            classic_wave = bool(cfg.general.get("classic_wave", False))
+        self.classic_wave = bool(classic_wave)
+        if self.classic_wave and classic_fused is False:
+            raise ValueError("classic_wave=True selects a kernel of the classic_fused "
+                             "path; classic_fused=False contradicts it")
         if classic_fused is None:
-            classic_fused = bool(cfg.general.get("classic_fused", False))
+            classic_fused = self.classic_wave or \
+                bool(cfg.general.get("classic_fused", False))
         self.classic_fused = bool(classic_fused)
         if self.classic_fused:
             self._classic_check()
+            if self.classic_wave:
+                self._classic_wave_check()
             # per-slot moments: the kernel accumulates each slot's own, the
             # save_mask weighting happens at reduction time
             self.cl_ob_sum = torch.zeros((self.B, D), dtype=torch.float64, device=d)
@@ -368,6 +383,22 @@ class GpuEngine:
                 "classic_fused supports the plain action head only (no FFBinned, no "
                 "FFIntegGausAction* policy)")
         self._classic_kind = 0 if isinstance(env, BatchedCartPole) else 1
+
+    def _classic_wave_check(self):
+        """The wave kernel's own coverage, asked of the library (the rule
+        lives in es_classic_wave_check alone)."""
+        lib = ops.hip()
+        if not hasattr(lib, "es_classic_wave_episode"):
+            raise RuntimeError(
+                "classic_wave=True needs es_classic_wave_episode, which the loaded HIP "
+                "library does not have (an earlier revision through ES_HIP_SO?)")
+        rc = lib.es_classic_wave_check(self.dims_arr.ctypes.data, len(self.dims_arr),
+                                       self.row_stride, int(self.fp32))
+        if rc != 0:
+            raise ValueError(
+                f"classic_wave covers nets whose layers are all at most 64 wide and "
+                f"whose parameter row fits 64 KB of LDS; got widths {list(self.dims)} "
+                f"(es_classic_wave_check returned {rc})")
 
     @staticmethod
     def _fp8_layout_ok(dims: List[int]) -> bool:
@@ -399,6 +430,7 @@ class GpuEngine:
             path, enc = "pair", "e4m3" if self.eps_fp8 else "bf16"
         else:
             path = "split" if self.split_dyn else "fused" if self.fused else \
+                "classic_wave" if self.classic_wave else \
                 "classic" if self.classic_fused else "generic"
             enc = "none"
         return {"weights": self.weights_dtype, "eps_encoding": enc, "path": path,
@@ -596,8 +628,9 @@ class GpuEngine:
             state, state2 = env.state.data_ptr(), None
         else:
             state, state2 = env.th.data_ptr(), env.thdot.data_ptr()
-        fn, name = (ops.hip().es_classic_episode_f32, "es_classic_episode_f32") \
-            if self.fp32 else (ops.hip().es_classic_episode, "es_classic_episode")
+        name = ("es_classic_wave_episode" if self.classic_wave else "es_classic_episode") + \
+            ("_f32" if self.fp32 else "")
+        fn = getattr(ops.hip(), name)
         ops.check(fn(
             state, state2, env._steps.data_ptr(), self.alive.data_ptr(),
             self.member_steps.data_ptr(), self.rew_total.data_ptr(),

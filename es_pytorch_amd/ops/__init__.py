@@ -247,6 +247,14 @@ def _bind_hip(lib):
         lib.es_classic_episode.restype = i32
         lib.es_classic_episode_f32.argtypes = lib.es_classic_episode.argtypes
         lib.es_classic_episode_f32.restype = i32
+    # wave-per-slot kernel for nets at most 64 wide: the same argument list;
+    # the check is (dims, ndims, row_stride, f32) -> what a launch would return
+    if hasattr(lib, "es_classic_wave_episode"):
+        for fn in (lib.es_classic_wave_episode, lib.es_classic_wave_episode_f32):
+            fn.argtypes = lib.es_classic_episode.argtypes
+            fn.restype = i32
+        lib.es_classic_wave_check.argtypes = [p, i32, i64, i32]
+        lib.es_classic_wave_check.restype = i32
     # fp32-weights entry points: the argument lists of their bf16 counterparts
     lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
     lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes

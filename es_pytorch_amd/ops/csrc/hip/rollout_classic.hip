@@ -14,60 +14,12 @@
 //
 // Only the plain action head (act_mode 0, no bins), and only output 0 of the
 // net is the action: both envs have one action dimension.
-#include "mlp_core.h"
+#include "classic_env.h"
 
-#define CLS_CARTPOLE 0
-#define CLS_PENDULUM 1
-#define CLS_MAXOB 4
 // slot slab behind the mlp carve: fp64 ob_sum[4], ob_sumsq[4], then float
 // st[4] (the env state), ob[4] (its observation), rew, member steps, env
 // steps, pad
 #define CLS_SLAB_BYTES (2 * CLS_MAXOB * 8 + 12 * 4)
-
-// The float32 values of the Python doubles the envs compute with.
-#define CP_GRAVITY 9.8f
-#define CP_MASSPOLE 0.1f
-#define CP_TOTAL_MASS ((float)(0.1 + 1.0))
-#define CP_LENGTH 0.5f
-#define CP_POLEMASS_LENGTH ((float)(0.1 * 0.5))
-#define CP_FORCE_MAG 10.0f
-#define CP_TAU 0.02f
-#define CP_FOUR_THIRDS ((float)(4.0 / 3.0))
-#define CP_THETA_THRESHOLD ((float)(12 * 2 * 3.141592653589793 / 360))
-#define CP_X_THRESHOLD 2.4f
-#define PD_MAX_SPEED 8.0f
-#define PD_MAX_TORQUE 2.0f
-#define PD_DT 0.05f
-#define PD_GRAV_COEF ((float)(3 * 10.0 / (2 * 1.0)))     // 3 g / (2 l)
-#define PD_TORQUE_COEF ((float)(3.0 / (1.0 * 1.0 * 1.0)))  // 3 / (m l^2)
-
-struct ClassicArgs {
-  float* state;         // CartPole (n, 4); Pendulum th (n)
-  float* state2;        // Pendulum thdot (n); CartPole: unused
-  float* env_steps;     // the env's own step counter (n)
-  float* alive;         // (n)
-  float* member_steps;  // (n)
-  float* rew_total;     // (n)
-  double* ob_sum;       // (n, D)
-  double* ob_sumsq;     // (n, D)
-  const void* weights;
-  const float* obmean;
-  const float* obstd;
-  const float* ac_std_dev;
-  const uint64_t* seed_dev;
-  uint64_t salt_base;
-  int64_t row_stride;
-  float ob_clip;
-  float env_max_steps;
-  int kind, n_steps, eps, act_final, noiseless_from;
-  MlpShape sh;
-};
-
-// Observation k of env state st (CartPole: the state; Pendulum st = th, thdot).
-__device__ __forceinline__ float classic_ob(int kind, const float* st, int k) {
-  if (kind == CLS_CARTPOLE) return st[k];
-  return k == 0 ? cosf(st[0]) : k == 1 ? sinf(st[0]) : st[1];
-}
 
 template <typename WT>
 __device__ __forceinline__ void classic_episode_body(const ClassicArgs& A) {
@@ -133,38 +85,7 @@ __device__ __forceinline__ void classic_episode_body(const ClassicArgs& A) {
         a += ac_std * es_actnoise(seed0 + A.salt_base + (uint64_t)t + 1, (uint64_t)b * nout);
     }
     if (tid == 0) {
-#pragma clang fp contract(off)
-      float r;
-      if (kind == CLS_CARTPOLE) {
-        // BatchedCartPole.step, op for op in fp32
-        const float force = a > 0.0f ? CP_FORCE_MAG : -CP_FORCE_MAG;
-        const float x = st[0], x_dot = st[1], theta = st[2], theta_dot = st[3];
-        const float costheta = cosf(theta), sintheta = sinf(theta);
-        const float temp =
-            (force + CP_POLEMASS_LENGTH * (theta_dot * theta_dot) * sintheta) / CP_TOTAL_MASS;
-        const float thetaacc =
-            (CP_GRAVITY * sintheta - costheta * temp) /
-            (CP_LENGTH *
-             (CP_FOUR_THIRDS - CP_MASSPOLE * (costheta * costheta) / CP_TOTAL_MASS));
-        const float xacc = temp - CP_POLEMASS_LENGTH * thetaacc * costheta / CP_TOTAL_MASS;
-        st[0] = x + CP_TAU * x_dot;
-        st[1] = x_dot + CP_TAU * xacc;
-        st[2] = theta + CP_TAU * theta_dot;
-        st[3] = theta_dot + CP_TAU * thetaacc;
-        r = 1.0f;
-      } else {
-        // BatchedPendulum.step; ob = (cos th, sin th, thdot) of the pre-step state
-        const float u = fclampf(a, -PD_MAX_TORQUE, PD_MAX_TORQUE);
-        const float th = st[0], thdot = st[1];
-        const float costh = ob[0], sinth = ob[1];
-        const float th_norm = atan2f(sinth, costh);
-        const float cost = th_norm * th_norm + 0.1f * (thdot * thdot) + 0.001f * (u * u);
-        float nd = thdot + (PD_GRAV_COEF * sinth + PD_TORQUE_COEF * u) * PD_DT;
-        nd = fclampf(nd, -PD_MAX_SPEED, PD_MAX_SPEED);
-        st[0] = th + nd * PD_DT;
-        st[1] = nd;
-        r = -cost;
-      }
+      const float r = classic_env_step(kind, st, ob, a);
       tot[0] += r;
       tot[1] += 1.0f;
       tot[2] += 1.0f;
@@ -222,36 +143,13 @@ static inline int classic_launch(bool f32, void* state, void* state2, void* env_
                                  int32_t eps, int32_t act_final, int32_t noiseless_from,
                                  void* stream) {
   ClassicArgs A;
-  int rc = mlp_shape_init(&A.sh, dims_host, ndims, row_stride);
+  int rc = classic_args_init(&A, f32, state, state2, env_steps, alive, member_steps,
+                             rew_total, ob_sum, ob_sumsq, weights, obmean, obstd, dims_host,
+                             ndims, row_stride, ob_clip, ac_std_dev, seed_dev, salt_base,
+                             env_kind, ob_dim, env_max_steps, n_steps, eps, act_final,
+                             noiseless_from);
   if (rc) return rc;
-  if (f32) mlp_shape_vec_f32(&A.sh, row_stride);
-  if (env_kind != CLS_CARTPOLE && env_kind != CLS_PENDULUM) return -113;
-  const int want_ob = env_kind == CLS_CARTPOLE ? 4 : 3;
-  if (ob_dim != want_ob || A.sh.dims[0] != want_ob) return -114;
-  if (A.sh.dims[A.sh.n_layers] < 1) return -115;
   if (n_slots <= 0 || n_steps <= 0) return 0;
-  A.state = (float*)state;
-  A.state2 = (float*)state2;
-  A.env_steps = (float*)env_steps;
-  A.alive = (float*)alive;
-  A.member_steps = (float*)member_steps;
-  A.rew_total = (float*)rew_total;
-  A.ob_sum = (double*)ob_sum;
-  A.ob_sumsq = (double*)ob_sumsq;
-  A.weights = weights;
-  A.obmean = (const float*)obmean;
-  A.obstd = (const float*)obstd;
-  A.ac_std_dev = (const float*)ac_std_dev;
-  A.seed_dev = (const uint64_t*)seed_dev;
-  A.salt_base = salt_base;
-  A.row_stride = row_stride;
-  A.ob_clip = ob_clip;
-  A.env_max_steps = (float)env_max_steps;
-  A.kind = env_kind;
-  A.n_steps = n_steps;
-  A.eps = eps > 0 ? eps : 1;
-  A.act_final = act_final;
-  A.noiseless_from = noiseless_from;
   const unsigned lds = (unsigned)(mlp_lds_bytes(A.sh.maxdim) + CLS_SLAB_BYTES);
   if (f32)
     classic_episode_f32_kernel<<<dim3((unsigned)n_slots), dim3(256), lds,

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Classic-control rollout bench: GpuEngine.step per generation on the generic
 path under hipGraph (one es_mlp_fwd launch plus a dozen torch kernels per env
-step) against classic_fused (one es_classic_episode launch), on one box.
+step), classic_fused (one es_classic_episode launch, a workgroup per slot) and
+classic_wave (one es_classic_wave_episode launch, a wavefront per slot; nets at
+most 64 wide), on one box.
 
-For every grid point two engines are built from the same seeds, one per mode,
+For every grid point the engines are built from the same seeds, one per mode,
 and their generations ALTERNATE (generic, fused, generic, ...) after a
 warm-up, so both see the same machine state. Each generation ends in a device
 synchronise inside engine.step; rollout_s and gen_s are the engine's own
@@ -18,6 +20,10 @@ spread (max - min within a mode, the larger of the two).
 
   python tools/classic_bench.py                     # the whole grid, both modes
   python tools/classic_bench.py --modes generic     # baseline only
+  python tools/classic_bench.py --modes fused wave  # block against wave kernel
+
+With two modes the later one in the order generic, fused, wave is the new one
+of the verdict line.
 """
 import argparse
 import json
@@ -30,6 +36,8 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 ENVS = {"cartpole": ("CartPole-v1", 500), "pendulum": ("Pendulum-v1", 200)}
+# mode -> numerics["path"], in the order old -> new
+PATHS = {"generic": "generic", "fused": "classic", "wave": "classic_wave"}
 
 
 def make_engine(dev, mode, env_name, ppg, layers, max_steps, seed):
@@ -56,9 +64,10 @@ def make_engine(dev, mode, env_name, ppg, layers, max_steps, seed):
     rs = np.random.RandomState(seed + 1)
     # "generic" is the constructor's default: built without the keyword, so
     # the same script times a revision from before the keyword existed
-    kw = {} if mode == "generic" else {"classic_fused": True}
+    kw = {"generic": {}, "fused": {"classic_fused": True},
+          "wave": {"classic_wave": True}}[mode]
     eng = GpuEngine(cfg, comm, policy, nt, env, rs, use_graph=True, **kw)
-    assert eng.numerics["path"] == ("generic" if mode == "generic" else "classic")
+    assert eng.numerics["path"] == PATHS[mode]
     return eng
 
 
@@ -74,7 +83,7 @@ def one_gen(eng):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--modes", nargs="+", default=["generic", "fused"],
-                   choices=["generic", "fused"])
+                   choices=list(PATHS))
     p.add_argument("--envs", nargs="+", default=["cartpole", "pendulum"], choices=list(ENVS))
     p.add_argument("--ppg", type=int, nargs="+", default=[64, 1024, 4096])
     p.add_argument("--net", default="32,32", help="hidden layer sizes, comma separated")
@@ -118,14 +127,16 @@ def main():
                       f"{ro.min():>9.5f} {ro.max():>9.5f} {row['gen_s_med']:>10.5f} "
                       f"{row['env_steps_per_s']:>12.4g} {row['ep_len']:>7.1f}", flush=True)
             if len(point) == 2:
-                s, e = (np.array(point[m]["rollout_s"]) for m in ("generic", "fused"))
+                old, new = (m for m in PATHS if m in point)
+                s, e = (np.array(point[m]["rollout_s"]) for m in (old, new))
                 spread = max(s.max() - s.min(), e.max() - e.min())
                 lead = s.min() - e.max()
-                verdict = {"env": env_key, "ppg": ppg, "net": layers, "lead_s": float(lead),
+                verdict = {"env": env_key, "ppg": ppg, "net": layers, "old": old, "new": new,
+                           "lead_s": float(lead),
                            "spread_s": float(spread), "clears_bar": bool(lead > 3 * spread),
                            "speedup_med": float(np.median(s) / np.median(e))}
                 rows.append(verdict)
-                print(f"      fastest generic - slowest fused = {lead:.5f} s, spread "
+                print(f"      fastest {old} - slowest {new} = {lead:.5f} s, spread "
                       f"{spread:.5f} s, bar (3x spread) "
                       f"{'cleared' if verdict['clears_bar'] else 'NOT cleared'}, "
                       f"median rollout speed-up {verdict['speedup_med']:.1f}x", flush=True)
