@@ -40,6 +40,14 @@ and pairs + p on ``bf16(theta) +- bf16(sigma*eps_p)``, streaming ONE
 sigma*eps row per policy plus the theta row the whole grid shares. Two bf16
 roundings instead of one; the gradient uses the unquantized noise, as on the
 single-policy bf16 pair path. Off by default.
+
+``tag_wave=True`` (or ``general.ma_tag_wave``; either weight dtype, implies
+rollout mode ``"episode"``) plays the generation with the wave-per-game kernel
+for small nets (``rollout_tag_wave.hip``, ``es_tag_wave_episode`` / ``_f32``):
+a wavefront owns a game, both member rows sit in LDS for the whole episode,
+and the step loop has no block barrier. It covers policies whose layers are
+all at most 64 wide; any other pair of nets is an error at construction, never
+a fallback to the block kernel. Off by default.
 """
 from __future__ import annotations
 
@@ -121,7 +129,8 @@ class MultiAgentGpuEngine:
     def __init__(self, cfg, comm: Comm, policies: List[Policy], nt: NoiseTable, env,
                  rs: np.random.RandomState, rollout_mode: Optional[str] = None,
                  weights_dtype: Optional[str] = None,
-                 pair_rollout: Optional[bool] = None):
+                 pair_rollout: Optional[bool] = None,
+                 tag_wave: Optional[bool] = None):
         self.cfg = cfg
         self.comm = comm
         self.nt = nt
@@ -130,8 +139,24 @@ class MultiAgentGpuEngine:
         self.device = nt.noise.device
         self.n_agents = len(policies)
         assert env.N_AGENTS == self.n_agents
+        if tag_wave is None:
+            tag_wave = cfg.general.get("ma_tag_wave", False)
+        if not isinstance(tag_wave, bool):
+            raise ValueError(f"ma_tag_wave must be true or false, got {tag_wave!r}")
+        if tag_wave and (cfg.general.get("ma_pair_rollout", False)
+                         if pair_rollout is None else pair_rollout) is True:
+            raise ValueError(
+                "ma_tag_wave and ma_pair_rollout select different kernels for the "
+                "same rollout (the wave kernel has no pair form) - set one of them")
         if rollout_mode is None:
-            rollout_mode = cfg.general.get("ma_rollout_mode", "step")
+            # the wave kernel plays whole episodes: it implies the mode
+            rollout_mode = cfg.general.get("ma_rollout_mode",
+                                           "episode" if tag_wave else "step")
+        if tag_wave and rollout_mode == "step":
+            raise ValueError(
+                "ma_tag_wave plays whole episodes in the wave-per-game kernel and "
+                "implies ma_rollout_mode='episode', got 'step' - drop "
+                "ma_rollout_mode='step' or leave ma_tag_wave off")
         if rollout_mode not in ("step", "episode"):
             raise ValueError(f"ma_rollout_mode must be 'step' or 'episode', got "
                              f"{rollout_mode!r}")
@@ -185,6 +210,12 @@ class MultiAgentGpuEngine:
                 "library does not have (an earlier revision's library?) - leave "
                 "ma_pair_rollout off or rebuild the library")
         self.pair_rollout = pair_rollout
+        if tag_wave and not hasattr(ops.hip(), "es_tag_wave_episode"):
+            raise RuntimeError(
+                "ma_tag_wave needs es_tag_wave_episode, which the loaded HIP library "
+                "does not have (an earlier revision's library?) - leave ma_tag_wave "
+                "off or rebuild the library")
+        self.tag_wave = tag_wave
 
         ppg = cfg.general.policies_per_gen
         assert ppg % comm.size == 0 and (ppg / comm.size) % 2 == 0
@@ -196,6 +227,8 @@ class MultiAgentGpuEngine:
         self.states = [_PolicyState(p, self.device, self.pairs, env.ob_dims[i], wdt,
                                     pair=self.pair_rollout)
                        for i, p in enumerate(policies)]
+        if self.tag_wave:
+            self._tag_wave_check()
         self.actions = [torch.empty((self.B, env.ac_dims[i]), dtype=torch.float32,
                                     device=self.device) for i in range(self.n_agents)]
         self.alive = torch.ones(self.B, dtype=torch.float32, device=self.device)
@@ -212,6 +245,20 @@ class MultiAgentGpuEngine:
         self.gen = 0
         self.timings = {}
 
+    def _tag_wave_check(self):
+        """The wave kernel's own coverage, asked of the library (the rule lives
+        in es_tag_wave_check alone)."""
+        s0, s1 = self.states
+        rc = ops.hip().es_tag_wave_check(
+            s0.dims_arr.ctypes.data, len(s0.dims_arr), s1.dims_arr.ctypes.data,
+            len(s1.dims_arr), s0.row_stride, s1.row_stride, int(self.fp32))
+        if rc != 0:
+            raise ValueError(
+                f"ma_tag_wave covers PursuitTag policies whose layers are all at most "
+                f"64 wide and whose two parameter rows fit 64 KB of LDS together; got "
+                f"widths {list(s0.dims)} and {list(s1.dims)} (es_tag_wave_check "
+                f"returned {rc}) - leave ma_tag_wave off for these nets")
+
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream if \
             self.device.type == "cuda" else None
@@ -222,7 +269,8 @@ class MultiAgentGpuEngine:
         if self.pair_rollout:
             return {"weights": "bf16", "eps_encoding": "bf16", "path": "tag_pair",
                     "rollout_mode": "episode"}
-        return {"weights": self.weights_dtype, "eps_encoding": "none", "path": "tag",
+        return {"weights": self.weights_dtype, "eps_encoding": "none",
+                "path": "tag_wave" if self.tag_wave else "tag",
                 "rollout_mode": self.rollout_mode}
 
     def _forward(self, i: int, obs: torch.Tensor, salt: int):
@@ -261,8 +309,9 @@ class MultiAgentGpuEngine:
                 self.seed_dev.data_ptr(), 0, self.n_agents, env.ob_dims[0], self.pairs, 1,
                 self.max_steps, 1, self.B - 1, self._stream()), "es_tag_pair_episode")
             return self._episode_sums()
-        fn, name = (ops.hip().es_tag_episode_f32, "es_tag_episode_f32") if self.fp32 \
-            else (ops.hip().es_tag_episode, "es_tag_episode")
+        name = ("es_tag_wave_episode" if self.tag_wave else "es_tag_episode") + \
+            ("_f32" if self.fp32 else "")
+        fn = getattr(ops.hip(), name)
         ops.check(fn(
             env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
             self.member_steps.data_ptr(), self.rew_total.data_ptr(),

@@ -235,6 +235,15 @@ def _bind_hip(lib):
                                             p, i32, p, i32, i64, i64, f32, f32, p, p, p,
                                             u64, i32, i32, i32, i32, i32, i32, i32, p]
         lib.es_tag_pair_episode.restype = i32
+    # wave-per-game kernel for policies at most 64 wide: es_tag_episode's
+    # argument list; the check is (dims0, ndims0, dims1, ndims1, row_stride0,
+    # row_stride1, f32) -> what a launch would return
+    if hasattr(lib, "es_tag_wave_episode"):
+        for fn in (lib.es_tag_wave_episode, lib.es_tag_wave_episode_f32):
+            fn.argtypes = lib.es_tag_episode.argtypes
+            fn.restype = i32
+        lib.es_tag_wave_check.argtypes = [p, i32, p, i32, i64, i64, i32]
+        lib.es_tag_wave_check.restype = i32
     # (state, state2, env_steps, alive, member_steps, rew_total, ob_sum,
     # ob_sumsq; weights, obmean, obstd, dims + ndims, row_stride, ob_clip,
     # ac_std_dev, seed_dev, salt_base; env_kind, ob_dim, env_max_steps,

@@ -14,27 +14,14 @@
 //
 // Only what PursuitTag needs: two agents, 8 observations each, the first two
 // outputs of each net are the action. Anything else is an argument error.
-#include "mlp_core.h"
+#include "tag_env.h"
 
-#define TAG_OB 8        // own p, own v, other p, other v
-#define TAG_AC 2
-#define TAG_ARENA 5.0f  // BatchedPursuitTag.ARENA
 // game slab behind the mlp carve: fp64 ob_sum[2][8], ob_sumsq[2][8], then
 // float p[2][2], v[2][2], act[2][2], rew[2], steps, pad[3]
 #define TAG_SLAB_BYTES (2 * 2 * TAG_OB * 8 + 16 * 4)
 // the pair kernel's dynamic LDS: four activation buffers and two 256x8
 // partial slabs (= 2 * mlp_lds_bytes), then one game slab per member
 #define TAG_PAIR_LDS_BYTES(maxdim) (2 * mlp_lds_bytes(maxdim) + 2 * TAG_SLAB_BYTES)
-
-struct TagPolicy {
-  const void* weights;  // member rows of the kernel's weight type, row_stride apart
-  const float* obmean;
-  const float* obstd;
-  const float* ac_std_dev;
-  int64_t row_stride;
-  float ob_clip;
-  MlpShape sh;
-};
 
 // Agent i's forward on the pre-step state: writes its two raw actions to
 // act[2i], act[2i+1]. Ends on a barrier, so bufA/bufB are free afterwards.
@@ -164,26 +151,6 @@ tag_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
     steps_g[b] = steps[0];
     alive_g[b] = alive ? 1.0f : 0.0f;
   }
-}
-
-// f32: the rows are float32 and a layer is quad-tiled only where its 16-B
-// loads are aligned for THIS policy's stride (mlp_shape_vec_f32).
-static inline int tag_policy_init(TagPolicy* P, bool f32, const void* weights,
-                                  const void* obmean, const void* obstd,
-                                  const void* ac_std_dev, const int32_t* dims_host,
-                                  int32_t ndims, int64_t row_stride, float ob_clip) {
-  int rc = mlp_shape_init(&P->sh, dims_host, ndims, row_stride);
-  if (rc) return rc;
-  if (f32) mlp_shape_vec_f32(&P->sh, row_stride);
-  if (P->sh.dims[0] != TAG_OB) return -110;
-  if (P->sh.dims[P->sh.n_layers] < TAG_AC) return -111;
-  P->weights = weights;
-  P->obmean = (const float*)obmean;
-  P->obstd = (const float*)obstd;
-  P->ac_std_dev = (const float*)ac_std_dev;
-  P->row_stride = row_stride;
-  P->ob_clip = ob_clip;
-  return 0;
 }
 
 static inline int tag_launch(bool f32, void* p, void* v, void* alive, void* steps,

@@ -18,6 +18,10 @@ sigma*eps rows; bf16 only). It alternates with the others and gets a verdict
 of its own against "episode": a pair block lasts as long as the longer of its
 two episodes and the grid has half as many blocks, so small points may lose.
 
+Mode "wave" is episode mode with tag_wave=True (es_tag_wave_episode: a
+wavefront per game, both member rows in LDS; nets at most 64 wide, either
+dtype). It gets a verdict against "episode" per dtype.
+
 The project's bar for a speed claim: the SLOWEST run of the new mode must
 lead the FASTEST run of the old one by at least three times the run-to-run
 spread (max - min within a mode, the larger of the two).
@@ -25,6 +29,7 @@ spread (max - min within a mode, the larger of the two).
   python tools/ma_bench.py                      # the whole grid, both modes
   python tools/ma_bench.py --modes step         # baseline only
   python tools/ma_bench.py --modes episode pair # pair sharing against per-game rows
+  python tools/ma_bench.py --modes episode wave --nets 32,32   # block against wave kernel
 """
 import argparse
 import json
@@ -72,12 +77,16 @@ def make_engine(dev, mode, ppg, layers, max_steps, seed, wdtype="bf16"):
     kw = {} if mode == "step" else {"rollout_mode": "episode"}
     if mode == "pair":
         kw["pair_rollout"] = True
+    if mode == "wave":
+        kw["tag_wave"] = True
     # likewise "bf16": a revision from before weights_dtype ran bf16 rows
     if wdtype != "bf16":
         kw["weights_dtype"] = wdtype
     eng = MultiAgentGpuEngine(cfg, comm, policies, nt, env, rs, **kw)
-    assert getattr(eng, "rollout_mode", "step") == ("episode" if mode == "pair" else mode)
+    assert getattr(eng, "rollout_mode", "step") == \
+        ("episode" if mode in ("pair", "wave") else mode)
     assert getattr(eng, "pair_rollout", False) == (mode == "pair")
+    assert getattr(eng, "tag_wave", False) == (mode == "wave")
     assert getattr(eng, "weights_dtype", "bf16") == wdtype
     return eng
 
@@ -94,7 +103,7 @@ def one_gen(eng):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--modes", nargs="+", default=["step", "episode"],
-                   choices=["step", "episode", "pair"])
+                   choices=["step", "episode", "pair", "wave"])
     p.add_argument("--weights-dtype", nargs="+", default=["bf16"],
                    choices=["bf16", "fp32"], help="member-row dtypes to alternate")
     p.add_argument("--ppg", type=int, nargs="+", default=[32, 1024, 4096])
@@ -173,6 +182,22 @@ def main():
                       f"{spread:.5f} s, bar (3x spread) "
                       f"{'cleared' if verdict['clears_bar'] else 'NOT cleared'}, "
                       f"median rollout episode / pair {verdict['speedup_med']:.2f}x",
+                      flush=True)
+            for w in args.weights_dtype:
+                if not all((m, w) in point for m in ("episode", "wave")):
+                    continue
+                e, q = (np.array(point[m, w]["rollout_s"]) for m in ("episode", "wave"))
+                spread = max(e.max() - e.min(), q.max() - q.min())
+                lead = e.min() - q.max()
+                verdict = {"ppg": ppg, "net": layers, "weights_dtype": w,
+                           "wave_vs_episode": True, "lead_s": float(lead),
+                           "spread_s": float(spread), "clears_bar": bool(lead > 3 * spread),
+                           "speedup_med": float(np.median(e) / np.median(q))}
+                rows.append(verdict)
+                print(f"      {w}: fastest episode - slowest wave = {lead:.5f} s, spread "
+                      f"{spread:.5f} s, bar (3x spread) "
+                      f"{'cleared' if verdict['clears_bar'] else 'NOT cleared'}, "
+                      f"median rollout episode / wave {verdict['speedup_med']:.2f}x",
                       flush=True)
             for m in args.modes:
                 if (m, "bf16") in point and (m, "fp32") in point:
