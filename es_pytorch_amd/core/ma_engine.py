@@ -294,36 +294,27 @@ class MultiAgentGpuEngine:
         assert env.p.is_contiguous() and env.v.is_contiguous()
         self.ep_ob_sum.zero_()
         self.ep_ob_sumsq.zero_()
-        if self.pair_rollout:
-            ops.check(ops.hip().es_tag_pair_episode(
-                env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
-                self.member_steps.data_ptr(), self.rew_total.data_ptr(),
-                self.ep_ob_sum.data_ptr(), self.ep_ob_sumsq.data_ptr(),
-                s0.theta_row.data_ptr(), s1.theta_row.data_ptr(),
-                s0.eps_rows.data_ptr(), s1.eps_rows.data_ptr(), s0.obmean.data_ptr(),
-                s1.obmean.data_ptr(), s0.obstd.data_ptr(), s1.obstd.data_ptr(),
-                s0.dims_arr.ctypes.data, len(s0.dims_arr), s1.dims_arr.ctypes.data,
-                len(s1.dims_arr), s0.row_stride, s1.row_stride,
+        state = (env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
+                 self.member_steps.data_ptr(), self.rew_total.data_ptr(),
+                 self.ep_ob_sum.data_ptr(), self.ep_ob_sumsq.data_ptr())
+        nets = (s0.obmean.data_ptr(), s1.obmean.data_ptr(), s0.obstd.data_ptr(),
+                s1.obstd.data_ptr(), s0.dims_arr.ctypes.data, len(s0.dims_arr),
+                s1.dims_arr.ctypes.data, len(s1.dims_arr), s0.row_stride, s1.row_stride,
                 float(s0.policy._module.ob_clip), float(s1.policy._module.ob_clip),
-                s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(),
-                self.seed_dev.data_ptr(), 0, self.n_agents, env.ob_dims[0], self.pairs, 1,
-                self.max_steps, 1, self.B - 1, self._stream()), "es_tag_pair_episode")
-            return self._episode_sums()
-        name = ("es_tag_wave_episode" if self.tag_wave else "es_tag_episode") + \
-            ("_f32" if self.fp32 else "")
-        fn = getattr(ops.hip(), name)
-        ops.check(fn(
-            env.p.data_ptr(), env.v.data_ptr(), self.alive.data_ptr(),
-            self.member_steps.data_ptr(), self.rew_total.data_ptr(),
-            self.ep_ob_sum.data_ptr(), self.ep_ob_sumsq.data_ptr(),
-            s0.weights.data_ptr(), s1.weights.data_ptr(), s0.obmean.data_ptr(),
-            s1.obmean.data_ptr(), s0.obstd.data_ptr(), s1.obstd.data_ptr(),
-            s0.dims_arr.ctypes.data, len(s0.dims_arr), s1.dims_arr.ctypes.data,
-            len(s1.dims_arr), s0.row_stride, s1.row_stride,
-            float(s0.policy._module.ob_clip), float(s1.policy._module.ob_clip),
-            s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(), self.seed_dev.data_ptr(),
-            0, self.n_agents, env.ob_dims[0], self.B, self.max_steps, 1, self.B - 1,
-            self._stream()), name)
+                s0.acstd_dev.data_ptr(), s1.acstd_dev.data_ptr(), self.seed_dev.data_ptr(),
+                0, self.n_agents, env.ob_dims[0])
+        tail = (self.max_steps, 1, self.B - 1, self._stream())
+        if self.pair_rollout:
+            name = "es_tag_pair_episode"
+            rows = (s0.theta_row.data_ptr(), s1.theta_row.data_ptr(),
+                    s0.eps_rows.data_ptr(), s1.eps_rows.data_ptr())
+            games = (self.pairs, 1)
+        else:
+            name = ("es_tag_wave_episode" if self.tag_wave else "es_tag_episode") + \
+                ("_f32" if self.fp32 else "")
+            rows = (s0.weights.data_ptr(), s1.weights.data_ptr())
+            games = (self.B,)
+        ops.check(getattr(ops.hip(), name)(*state, *rows, *nets, *games, *tail), name)
         return self._episode_sums()
 
     def _episode_sums(self):

@@ -1,7 +1,8 @@
 // What the classic-control episode kernels share (rollout_classic.hip: a
 // workgroup per slot; rollout_classic_wave.hip: a wavefront per slot): the env
-// constants, the launch arguments and their checks, the observation and the
-// env step of BatchedCartPole / BatchedPendulum (envs/classic.py).
+// constants, the observation and the env step of BatchedCartPole /
+// BatchedPendulum (envs/classic.py), the launch arguments and their checks,
+// and the C argument list of the entry points.
 #pragma once
 #include "mlp_core.h"
 
@@ -94,47 +95,84 @@ __device__ __forceinline__ float classic_env_step(int kind, float* st, const flo
   return r;
 }
 
+// One call's arguments, in the order of CLASSIC_EPISODE_ENTRY's list.
+struct ClassicCall {
+  void *state, *state2, *env_steps, *alive, *member_steps, *rew_total, *ob_sum, *ob_sumsq;
+  const void *weights, *obmean, *obstd;
+  const int32_t* dims_host;
+  int32_t ndims;
+  int64_t row_stride;
+  float ob_clip;
+  const void *ac_std_dev, *seed_dev;
+  uint64_t salt_base;
+  int32_t env_kind, ob_dim, env_max_steps, n_slots, n_steps, eps, act_final, noiseless_from;
+  void* stream;
+};
+
 // The argument checks both launchers make, in this order, and the fill of A.
 // 0: launch; a negative code: launch nothing.
-static inline int classic_args_init(ClassicArgs* Ap, bool f32, void* state, void* state2,
-                                    void* env_steps, void* alive, void* member_steps,
-                                    void* rew_total, void* ob_sum, void* ob_sumsq,
-                                    const void* weights, const void* obmean,
-                                    const void* obstd, const int32_t* dims_host,
-                                    int32_t ndims, int64_t row_stride, float ob_clip,
-                                    const void* ac_std_dev, const void* seed_dev,
-                                    uint64_t salt_base, int32_t env_kind, int32_t ob_dim,
-                                    int32_t env_max_steps, int32_t n_steps, int32_t eps,
-                                    int32_t act_final, int32_t noiseless_from) {
+static inline int classic_args_init(ClassicArgs* Ap, bool f32, const ClassicCall& c) {
   ClassicArgs& A = *Ap;
-  int rc = mlp_shape_init(&A.sh, dims_host, ndims, row_stride);
+  int rc = mlp_shape_init(&A.sh, c.dims_host, c.ndims, c.row_stride);
   if (rc) return rc;
-  if (f32) mlp_shape_vec_f32(&A.sh, row_stride);
-  if (env_kind != CLS_CARTPOLE && env_kind != CLS_PENDULUM) return -113;
-  const int want_ob = env_kind == CLS_CARTPOLE ? 4 : 3;
-  if (ob_dim != want_ob || A.sh.dims[0] != want_ob) return -114;
+  if (f32) mlp_shape_vec_f32(&A.sh, c.row_stride);
+  if (c.env_kind != CLS_CARTPOLE && c.env_kind != CLS_PENDULUM) return -113;
+  const int want_ob = c.env_kind == CLS_CARTPOLE ? 4 : 3;
+  if (c.ob_dim != want_ob || A.sh.dims[0] != want_ob) return -114;
   if (A.sh.dims[A.sh.n_layers] < 1) return -115;
-  A.state = (float*)state;
-  A.state2 = (float*)state2;
-  A.env_steps = (float*)env_steps;
-  A.alive = (float*)alive;
-  A.member_steps = (float*)member_steps;
-  A.rew_total = (float*)rew_total;
-  A.ob_sum = (double*)ob_sum;
-  A.ob_sumsq = (double*)ob_sumsq;
-  A.weights = weights;
-  A.obmean = (const float*)obmean;
-  A.obstd = (const float*)obstd;
-  A.ac_std_dev = (const float*)ac_std_dev;
-  A.seed_dev = (const uint64_t*)seed_dev;
-  A.salt_base = salt_base;
-  A.row_stride = row_stride;
-  A.ob_clip = ob_clip;
-  A.env_max_steps = (float)env_max_steps;
-  A.kind = env_kind;
-  A.n_steps = n_steps;
-  A.eps = eps > 0 ? eps : 1;
-  A.act_final = act_final;
-  A.noiseless_from = noiseless_from;
+  A.state = (float*)c.state;
+  A.state2 = (float*)c.state2;
+  A.env_steps = (float*)c.env_steps;
+  A.alive = (float*)c.alive;
+  A.member_steps = (float*)c.member_steps;
+  A.rew_total = (float*)c.rew_total;
+  A.ob_sum = (double*)c.ob_sum;
+  A.ob_sumsq = (double*)c.ob_sumsq;
+  A.weights = c.weights;
+  A.obmean = (const float*)c.obmean;
+  A.obstd = (const float*)c.obstd;
+  A.ac_std_dev = (const float*)c.ac_std_dev;
+  A.seed_dev = (const uint64_t*)c.seed_dev;
+  A.salt_base = c.salt_base;
+  A.row_stride = c.row_stride;
+  A.ob_clip = c.ob_clip;
+  A.env_max_steps = (float)c.env_max_steps;
+  A.kind = c.env_kind;
+  A.n_steps = c.n_steps;
+  A.eps = c.eps > 0 ? c.eps : 1;
+  A.act_final = c.act_final;
+  A.noiseless_from = c.noiseless_from;
   return 0;
 }
+
+// Defines the extern "C" entry point `name`, which calls
+// launcher(f32, const ClassicCall&). The argument list of every entry point
+// (es_classic_episode[_f32], es_classic_wave_episode[_f32]):
+//
+// State, (n_slots, ...) each, read at launch and written back at the end:
+// CartPole (env_kind 0, ob_dim 4): state float (., 4) = x, x_dot, theta,
+// theta_dot; state2 unused. Pendulum (env_kind 1, ob_dim 3): state = th,
+// state2 = thdot, float (.) each. env_steps (the env's own counter, which ends
+// the episode at env_max_steps), alive, member_steps, rew_total float (.);
+// ob_sum, ob_sumsq double (., ob_dim). weights: (rows, row_stride), bf16 or,
+// for an _f32 entry point, float32; slot b on row b / eps; obmean/obstd float
+// (ob_dim); ac_std_dev float (1) or null.
+// Step t of the launch (0-based) draws the action noise of slots below
+// noiseless_from with key *seed_dev + salt_base + t + 1 at counter b * A, A
+// the net's output width: es_mlp_fwd's draw at salt salt_base + t + 1.
+#define CLASSIC_EPISODE_ENTRY(name, launcher, f32)                                          \
+  extern "C" int name(                                                                      \
+      void* state, void* state2, void* env_steps, void* alive, void* member_steps,          \
+      void* rew_total, void* ob_sum, void* ob_sumsq, const void* weights,                   \
+      const void* obmean, const void* obstd, const int32_t* dims_host, int32_t ndims,       \
+      int64_t row_stride, float ob_clip, const void* ac_std_dev, const void* seed_dev,      \
+      uint64_t salt_base, int32_t env_kind, int32_t ob_dim, int32_t env_max_steps,          \
+      int32_t n_slots, int32_t n_steps, int32_t eps, int32_t act_final,                     \
+      int32_t noiseless_from, void* stream) {                                               \
+    return launcher(                                                                        \
+        f32, ClassicCall{state, state2, env_steps, alive, member_steps, rew_total, ob_sum,  \
+                         ob_sumsq, weights, obmean, obstd, dims_host, ndims, row_stride,    \
+                         ob_clip, ac_std_dev, seed_dev, salt_base, env_kind, ob_dim,        \
+                         env_max_steps, n_slots, n_steps, eps, act_final, noiseless_from,   \
+                         stream});                                                          \
+  }

@@ -132,76 +132,22 @@ __global__ void __launch_bounds__(256) classic_episode_f32_kernel(ClassicArgs A)
   classic_episode_body<float>(A);
 }
 
-static inline int classic_launch(bool f32, void* state, void* state2, void* env_steps,
-                                 void* alive, void* member_steps, void* rew_total,
-                                 void* ob_sum, void* ob_sumsq, const void* weights,
-                                 const void* obmean, const void* obstd,
-                                 const int32_t* dims_host, int32_t ndims, int64_t row_stride,
-                                 float ob_clip, const void* ac_std_dev, const void* seed_dev,
-                                 uint64_t salt_base, int32_t env_kind, int32_t ob_dim,
-                                 int32_t env_max_steps, int32_t n_slots, int32_t n_steps,
-                                 int32_t eps, int32_t act_final, int32_t noiseless_from,
-                                 void* stream) {
+static inline int classic_launch(bool f32, const ClassicCall& c) {
   ClassicArgs A;
-  int rc = classic_args_init(&A, f32, state, state2, env_steps, alive, member_steps,
-                             rew_total, ob_sum, ob_sumsq, weights, obmean, obstd, dims_host,
-                             ndims, row_stride, ob_clip, ac_std_dev, seed_dev, salt_base,
-                             env_kind, ob_dim, env_max_steps, n_steps, eps, act_final,
-                             noiseless_from);
+  const int rc = classic_args_init(&A, f32, c);
   if (rc) return rc;
-  if (n_slots <= 0 || n_steps <= 0) return 0;
+  if (c.n_slots <= 0 || c.n_steps <= 0) return 0;
   const unsigned lds = (unsigned)(mlp_lds_bytes(A.sh.maxdim) + CLS_SLAB_BYTES);
   if (f32)
-    classic_episode_f32_kernel<<<dim3((unsigned)n_slots), dim3(256), lds,
-                                 (hipStream_t)stream>>>(A);
+    classic_episode_f32_kernel<<<dim3((unsigned)c.n_slots), dim3(256), lds,
+                                 (hipStream_t)c.stream>>>(A);
   else
-    classic_episode_kernel<<<dim3((unsigned)n_slots), dim3(256), lds,
-                             (hipStream_t)stream>>>(A);
+    classic_episode_kernel<<<dim3((unsigned)c.n_slots), dim3(256), lds,
+                             (hipStream_t)c.stream>>>(A);
   ES_CHECK_LAUNCH();
   return 0;
 }
 
-// State, (n_slots, ...) each, read at launch and written back at the end:
-// CartPole (env_kind 0, ob_dim 4): state float (., 4) = x, x_dot, theta,
-// theta_dot; state2 unused. Pendulum (env_kind 1, ob_dim 3): state = th,
-// state2 = thdot, float (.) each. env_steps (the env's own counter, which ends
-// the episode at env_max_steps), alive, member_steps, rew_total float (.);
-// ob_sum, ob_sumsq double (., ob_dim). weights: bf16 (rows, row_stride), slot
-// b on row b / eps; obmean/obstd float (ob_dim); ac_std_dev float (1) or null.
-// Step t of the launch (0-based) draws the action noise of slots below
-// noiseless_from with key *seed_dev + salt_base + t + 1 at counter b * A, A
-// the net's output width: es_mlp_fwd's draw at salt salt_base + t + 1.
-extern "C" int es_classic_episode(void* state, void* state2, void* env_steps, void* alive,
-                                  void* member_steps, void* rew_total, void* ob_sum,
-                                  void* ob_sumsq, const void* weights, const void* obmean,
-                                  const void* obstd, const int32_t* dims_host, int32_t ndims,
-                                  int64_t row_stride, float ob_clip, const void* ac_std_dev,
-                                  const void* seed_dev, uint64_t salt_base, int32_t env_kind,
-                                  int32_t ob_dim, int32_t env_max_steps, int32_t n_slots,
-                                  int32_t n_steps, int32_t eps, int32_t act_final,
-                                  int32_t noiseless_from, void* stream) {
-  return classic_launch(false, state, state2, env_steps, alive, member_steps, rew_total,
-                        ob_sum, ob_sumsq, weights, obmean, obstd, dims_host, ndims,
-                        row_stride, ob_clip, ac_std_dev, seed_dev, salt_base, env_kind,
-                        ob_dim, env_max_steps, n_slots, n_steps, eps, act_final,
-                        noiseless_from, stream);
-}
-
-// fp32 rows: same argument list; `weights` is float32 (rows, row_stride).
-extern "C" int es_classic_episode_f32(void* state, void* state2, void* env_steps,
-                                      void* alive, void* member_steps, void* rew_total,
-                                      void* ob_sum, void* ob_sumsq, const void* weights,
-                                      const void* obmean, const void* obstd,
-                                      const int32_t* dims_host, int32_t ndims,
-                                      int64_t row_stride, float ob_clip,
-                                      const void* ac_std_dev, const void* seed_dev,
-                                      uint64_t salt_base, int32_t env_kind, int32_t ob_dim,
-                                      int32_t env_max_steps, int32_t n_slots, int32_t n_steps,
-                                      int32_t eps, int32_t act_final, int32_t noiseless_from,
-                                      void* stream) {
-  return classic_launch(true, state, state2, env_steps, alive, member_steps, rew_total,
-                        ob_sum, ob_sumsq, weights, obmean, obstd, dims_host, ndims,
-                        row_stride, ob_clip, ac_std_dev, seed_dev, salt_base, env_kind,
-                        ob_dim, env_max_steps, n_slots, n_steps, eps, act_final,
-                        noiseless_from, stream);
-}
+// Argument list and contract: CLASSIC_EPISODE_ENTRY (classic_env.h).
+CLASSIC_EPISODE_ENTRY(es_classic_episode, classic_launch, false)
+CLASSIC_EPISODE_ENTRY(es_classic_episode_f32, classic_launch, true)

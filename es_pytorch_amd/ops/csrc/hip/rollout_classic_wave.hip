@@ -31,10 +31,6 @@
 #include "classic_env.h"
 #include "wave_mlp.h"
 
-#define CLW_MAXW 64            // widest layer the lane mapping covers
-#define CLW_LDS_BUDGET 65536   // dynamic LDS of a block
-#define CLW_WAVES 4            // waves of a block
-
 struct ClassicWaveArgs {
   ClassicArgs a;
   int n_slots;
@@ -136,48 +132,29 @@ classic_wave_episode_kernel(ClassicWaveArgs W) {
   classic_wave_episode_body<WT>(W);
 }
 
-// Coverage, the one place it is decided: 0 and the launch geometry, or -116.
-static inline int classic_wave_geometry(const MlpShape& sh, bool f32, int* spb,
-                                        int* region_bytes, int* n_params) {
-  for (int l = 0; l <= sh.n_layers; ++l)
-    if (sh.dims[l] > CLW_MAXW) return -116;
-  const int64_t n = sh.boff[sh.n_layers - 1] + sh.dims[sh.n_layers];
-  const int64_t region = (n * (f32 ? 4 : 2) + 15) & ~(int64_t)15;
-  if (region > CLW_LDS_BUDGET) return -116;
-  *spb = 4 * region <= CLW_LDS_BUDGET ? 4 : 2 * region <= CLW_LDS_BUDGET ? 2 : 1;
-  *region_bytes = (int)region;
-  *n_params = (int)n;
-  return 0;
+// The coverage (wave_mlp.h): 0 and the geometry of W, or -116.
+static inline int classic_wave_geometry(const MlpShape& sh, bool f32, ClassicWaveArgs* W) {
+  W->n_params = wave_row_elems(sh);
+  if (W->n_params < 0) return W->n_params;
+  W->region_bytes = wave_row_bytes(W->n_params, f32);
+  W->spb = wave_regions_per_block(W->region_bytes);
+  return W->spb < 0 ? W->spb : 0;
 }
 
-static inline int classic_wave_launch(bool f32, void* state, void* state2, void* env_steps,
-                                      void* alive, void* member_steps, void* rew_total,
-                                      void* ob_sum, void* ob_sumsq, const void* weights,
-                                      const void* obmean, const void* obstd,
-                                      const int32_t* dims_host, int32_t ndims,
-                                      int64_t row_stride, float ob_clip,
-                                      const void* ac_std_dev, const void* seed_dev,
-                                      uint64_t salt_base, int32_t env_kind, int32_t ob_dim,
-                                      int32_t env_max_steps, int32_t n_slots, int32_t n_steps,
-                                      int32_t eps, int32_t act_final, int32_t noiseless_from,
-                                      void* stream) {
+static inline int classic_wave_launch(bool f32, const ClassicCall& c) {
   ClassicWaveArgs W;
-  int rc = classic_args_init(&W.a, f32, state, state2, env_steps, alive, member_steps,
-                             rew_total, ob_sum, ob_sumsq, weights, obmean, obstd, dims_host,
-                             ndims, row_stride, ob_clip, ac_std_dev, seed_dev, salt_base,
-                             env_kind, ob_dim, env_max_steps, n_steps, eps, act_final,
-                             noiseless_from);
+  int rc = classic_args_init(&W.a, f32, c);
   if (rc) return rc;
-  rc = classic_wave_geometry(W.a.sh, f32, &W.spb, &W.region_bytes, &W.n_params);
+  rc = classic_wave_geometry(W.a.sh, f32, &W);
   if (rc) return rc;
-  if (n_slots <= 0 || n_steps <= 0) return 0;
-  W.n_slots = n_slots;
-  const dim3 grid((unsigned)((n_slots + W.spb - 1) / W.spb)), block(64 * CLW_WAVES);
+  if (c.n_slots <= 0 || c.n_steps <= 0) return 0;
+  W.n_slots = c.n_slots;
+  const dim3 grid((unsigned)((c.n_slots + W.spb - 1) / W.spb)), block(64 * WAVE_WAVES);
   const unsigned lds = (unsigned)(W.spb * W.region_bytes);
   if (f32)
-    classic_wave_episode_kernel<float><<<grid, block, lds, (hipStream_t)stream>>>(W);
+    classic_wave_episode_kernel<float><<<grid, block, lds, (hipStream_t)c.stream>>>(W);
   else
-    classic_wave_episode_kernel<uint16_t><<<grid, block, lds, (hipStream_t)stream>>>(W);
+    classic_wave_episode_kernel<uint16_t><<<grid, block, lds, (hipStream_t)c.stream>>>(W);
   ES_CHECK_LAUNCH();
   return 0;
 }
@@ -190,45 +167,10 @@ extern "C" int es_classic_wave_check(const int32_t* dims_host, int32_t ndims,
   int rc = mlp_shape_init(&sh, dims_host, ndims, row_stride);
   if (rc) return rc;
   if (sh.dims[sh.n_layers] < 1) return -115;
-  int spb, region, n;
-  return classic_wave_geometry(sh, f32 != 0, &spb, &region, &n);
+  ClassicWaveArgs W;
+  return classic_wave_geometry(sh, f32 != 0, &W);
 }
 
-// Argument list and contract of es_classic_episode (rollout_classic.hip).
-extern "C" int es_classic_wave_episode(void* state, void* state2, void* env_steps,
-                                       void* alive, void* member_steps, void* rew_total,
-                                       void* ob_sum, void* ob_sumsq, const void* weights,
-                                       const void* obmean, const void* obstd,
-                                       const int32_t* dims_host, int32_t ndims,
-                                       int64_t row_stride, float ob_clip,
-                                       const void* ac_std_dev, const void* seed_dev,
-                                       uint64_t salt_base, int32_t env_kind, int32_t ob_dim,
-                                       int32_t env_max_steps, int32_t n_slots,
-                                       int32_t n_steps, int32_t eps, int32_t act_final,
-                                       int32_t noiseless_from, void* stream) {
-  return classic_wave_launch(false, state, state2, env_steps, alive, member_steps, rew_total,
-                             ob_sum, ob_sumsq, weights, obmean, obstd, dims_host, ndims,
-                             row_stride, ob_clip, ac_std_dev, seed_dev, salt_base, env_kind,
-                             ob_dim, env_max_steps, n_slots, n_steps, eps, act_final,
-                             noiseless_from, stream);
-}
-
-// fp32 rows: same argument list; `weights` is float32 (rows, row_stride).
-extern "C" int es_classic_wave_episode_f32(void* state, void* state2, void* env_steps,
-                                           void* alive, void* member_steps, void* rew_total,
-                                           void* ob_sum, void* ob_sumsq, const void* weights,
-                                           const void* obmean, const void* obstd,
-                                           const int32_t* dims_host, int32_t ndims,
-                                           int64_t row_stride, float ob_clip,
-                                           const void* ac_std_dev, const void* seed_dev,
-                                           uint64_t salt_base, int32_t env_kind,
-                                           int32_t ob_dim, int32_t env_max_steps,
-                                           int32_t n_slots, int32_t n_steps, int32_t eps,
-                                           int32_t act_final, int32_t noiseless_from,
-                                           void* stream) {
-  return classic_wave_launch(true, state, state2, env_steps, alive, member_steps, rew_total,
-                             ob_sum, ob_sumsq, weights, obmean, obstd, dims_host, ndims,
-                             row_stride, ob_clip, ac_std_dev, seed_dev, salt_base, env_kind,
-                             ob_dim, env_max_steps, n_slots, n_steps, eps, act_final,
-                             noiseless_from, stream);
-}
+// Argument list and contract: CLASSIC_EPISODE_ENTRY (classic_env.h).
+CLASSIC_EPISODE_ENTRY(es_classic_wave_episode, classic_wave_launch, false)
+CLASSIC_EPISODE_ENTRY(es_classic_wave_episode_f32, classic_wave_launch, true)

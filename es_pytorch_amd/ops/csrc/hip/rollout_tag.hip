@@ -31,9 +31,7 @@ __device__ __forceinline__ void tag_agent_forward(
     float* bufB, float* partial, float mean_k, float std_k, uint64_t seed,
     int act_final, int noiseless_from, int tid) {
   if (tid < TAG_OB) {
-    // st = p[2][2] v[2][2]: own p, own v, other p, other v
-    const int who = (tid & 4) ? 1 - i : i;
-    const float ob = st[((tid >> 1) & 1) * 4 + who * 2 + (tid & 1)];
+    const float ob = st[tag_ob_index(i, tid)];
     bufA[tid] = fclampf((ob - mean_k) / std_k, -P.ob_clip, P.ob_clip);
   }
   __syncthreads();
@@ -107,27 +105,18 @@ tag_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
     {
       // BatchedPursuitTag.step, op for op in fp32
 #pragma clang fp contract(off)
-      if (tid < 4) {
-        const float a = fclampf(act[tid], -1.0f, 1.0f);
-        const float vn = 0.8f * st[4 + tid] + a * 0.1f * 5.0f;
-        st[4 + tid] = vn;
-        st[tid] = fclampf(st[tid] + vn * 0.1f, -TAG_ARENA, TAG_ARENA);
-      }
+      if (tid < 4) tag_move(st[tid], st[4 + tid], act[tid]);
       __syncthreads();
       const float dx = st[0] - st[2], dy = st[1] - st[3];
       const float d = sqrtf(dx * dx + dy * dy);
-      const bool caught = d < 0.3f;
-      const float bonus = caught ? 10.0f : 0.0f;
+      const bool caught = d < TAG_CATCH_DIST;
       if (tid == 0) {
-        rew[0] += -d + bonus;
-        rew[1] += d - bonus;
+        tag_reward(d, caught, rew[0], rew[1]);
         steps[0] += 1.0f;
       }
       if (tid < 2 * TAG_OB) {
         // post-step observation of agent tid / 8, the terminal one included
-        const int i = tid >> 3, k = tid & 7;
-        const int who = (k & 4) ? 1 - i : i;
-        const double ob = (double)st[((k >> 1) & 1) * 4 + who * 2 + (k & 1)];
+        const double ob = (double)st[tag_ob_index(tid >> 3, tid & 7)];
         obsum[tid] += ob;
         obsq[tid] += ob * ob;
       }
@@ -153,88 +142,29 @@ tag_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
   }
 }
 
-static inline int tag_launch(bool f32, void* p, void* v, void* alive, void* steps,
-                             void* rew_total, void* ob_sum, void* ob_sumsq,
-                             const void* weights0, const void* weights1,
-                             const void* obmean0, const void* obmean1, const void* obstd0,
-                             const void* obstd1, const int32_t* dims0_host, int32_t ndims0,
-                             const int32_t* dims1_host, int32_t ndims1, int64_t row_stride0,
-                             int64_t row_stride1, float ob_clip0, float ob_clip1,
-                             const void* ac_std_dev0, const void* ac_std_dev1,
-                             const void* seed_dev, uint64_t salt_base, int32_t n_agents,
-                             int32_t ob_dim, int32_t n_games, int32_t n_steps,
-                             int32_t act_final, int32_t noiseless_from, void* stream) {
-  if (n_agents != 2) return -112;
-  if (ob_dim != TAG_OB) return -110;
+static inline int tag_launch(bool f32, const TagCall& c) {
   TagPolicy P0, P1;
-  int rc = tag_policy_init(&P0, f32, weights0, obmean0, obstd0, ac_std_dev0, dims0_host,
-                           ndims0, row_stride0, ob_clip0);
+  const int rc = tag_policies_init(c, f32, &P0, &P1);
   if (rc) return rc;
-  rc = tag_policy_init(&P1, f32, weights1, obmean1, obstd1, ac_std_dev1, dims1_host, ndims1,
-                       row_stride1, ob_clip1);
-  if (rc) return rc;
-  if (n_games <= 0 || n_steps <= 0) return 0;
+  if (c.n_games <= 0 || c.n_steps <= 0) return 0;
   const int maxdim = std::max(P0.sh.maxdim, P1.sh.maxdim);
   const unsigned lds = (unsigned)(mlp_lds_bytes(maxdim) + TAG_SLAB_BYTES);
   auto kernel = f32 ? tag_episode_kernel<float> : tag_episode_kernel<uint16_t>;
-  kernel<<<dim3((unsigned)n_games), dim3(256), lds, (hipStream_t)stream>>>(
-      (float*)p, (float*)v, (float*)alive, (float*)steps, (float*)rew_total,
-      (double*)ob_sum, (double*)ob_sumsq, P0, P1, maxdim, (const uint64_t*)seed_dev,
-      salt_base, n_steps, act_final, noiseless_from);
+  kernel<<<dim3((unsigned)c.n_games), dim3(256), lds, (hipStream_t)c.stream>>>(
+      (float*)c.p, (float*)c.v, (float*)c.alive, (float*)c.steps, (float*)c.rew_total,
+      (double*)c.ob_sum, (double*)c.ob_sumsq, P0, P1, maxdim, (const uint64_t*)c.seed_dev,
+      c.salt_base, c.n_steps, c.act_final, c.noiseless_from);
   ES_CHECK_LAUNCH();
   return 0;
 }
 
-// State, (n_games, ...) each, read at launch and written back at the end:
-// p, v float (.,2,2); alive, steps float (.); rew_total float (.,2);
-// ob_sum, ob_sumsq double (.,2,8). Policy i: bf16 weights (n_games,
-// row_stride_i), obmean/obstd float (8), ac_std_dev_i float (1) or null.
-// Step t of the launch (0-based) draws agent i's action noise with key
-// *seed_dev + (salt_base + t + 1) * 2 + i. n_agents and ob_dim are what the
-// caller's env has; only 2 and 8 are implemented.
-extern "C" int es_tag_episode(void* p, void* v, void* alive, void* steps, void* rew_total,
-                              void* ob_sum, void* ob_sumsq, const void* weights0,
-                              const void* weights1, const void* obmean0,
-                              const void* obmean1, const void* obstd0, const void* obstd1,
-                              const int32_t* dims0_host, int32_t ndims0,
-                              const int32_t* dims1_host, int32_t ndims1,
-                              int64_t row_stride0, int64_t row_stride1, float ob_clip0,
-                              float ob_clip1, const void* ac_std_dev0,
-                              const void* ac_std_dev1, const void* seed_dev,
-                              uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
-                              int32_t n_games, int32_t n_steps, int32_t act_final,
-                              int32_t noiseless_from, void* stream) {
-  return tag_launch(false, p, v, alive, steps, rew_total, ob_sum, ob_sumsq, weights0,
-                    weights1, obmean0, obmean1, obstd0, obstd1, dims0_host, ndims0,
-                    dims1_host, ndims1, row_stride0, row_stride1, ob_clip0, ob_clip1,
-                    ac_std_dev0, ac_std_dev1, seed_dev, salt_base, n_agents, ob_dim, n_games,
-                    n_steps, act_final, noiseless_from, stream);
-}
+// Argument list and contract: TAG_EPISODE_ENTRY (tag_env.h). bf16 rows.
+TAG_EPISODE_ENTRY(es_tag_episode, tag_launch, false)
 
-// fp32 rows: same argument list and return codes; weights_i is float32
-// (n_games, row_stride_i), row_stride_i counted in floats. A policy whose
-// stride is no multiple of 4 floats, and any layer whose weight block is not
-// 16-B aligned in the row or whose width is no multiple of 4, takes the
-// scalar walks.
-extern "C" int es_tag_episode_f32(void* p, void* v, void* alive, void* steps,
-                                  void* rew_total, void* ob_sum, void* ob_sumsq,
-                                  const void* weights0, const void* weights1,
-                                  const void* obmean0, const void* obmean1,
-                                  const void* obstd0, const void* obstd1,
-                                  const int32_t* dims0_host, int32_t ndims0,
-                                  const int32_t* dims1_host, int32_t ndims1,
-                                  int64_t row_stride0, int64_t row_stride1, float ob_clip0,
-                                  float ob_clip1, const void* ac_std_dev0,
-                                  const void* ac_std_dev1, const void* seed_dev,
-                                  uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
-                                  int32_t n_games, int32_t n_steps, int32_t act_final,
-                                  int32_t noiseless_from, void* stream) {
-  return tag_launch(true, p, v, alive, steps, rew_total, ob_sum, ob_sumsq, weights0,
-                    weights1, obmean0, obmean1, obstd0, obstd1, dims0_host, ndims0,
-                    dims1_host, ndims1, row_stride0, row_stride1, ob_clip0, ob_clip1,
-                    ac_std_dev0, ac_std_dev1, seed_dev, salt_base, n_agents, ob_dim, n_games,
-                    n_steps, act_final, noiseless_from, stream);
-}
+// fp32 rows: same return codes. A policy whose stride is no multiple of 4
+// floats, and any layer whose weight block is not 16-B aligned in the row or
+// whose width is no multiple of 4, takes the scalar walks.
+TAG_EPISODE_ENTRY(es_tag_episode_f32, tag_launch, true)
 
 // ---- antithetic-pair form ---------------------------------------------------
 // One workgroup plays BOTH games of an antithetic pair: block g < n_pairs has
@@ -261,8 +191,7 @@ __device__ __forceinline__ void tag_pair_agent_forward(
     bool mine, int m, int lt, const float* st, float* act, const TagPairLds& L, float mean_k,
     float std_k, uint64_t seed, int act_final, int noiseless_from, int tid) {
   if (lt < TAG_OB) {
-    const int who = (lt & 4) ? 1 - i : i;
-    const float ob = st[((lt >> 1) & 1) * 4 + who * 2 + (lt & 1)];
+    const float ob = st[tag_ob_index(i, lt)];
     (m ? L.bufAm : L.bufAp)[lt] =
         mine ? fclampf((ob - mean_k) / std_k, -P.ob_clip, P.ob_clip) : 0.0f;
   }
@@ -361,31 +290,21 @@ tag_pair_episode_kernel(float* __restrict__ p_g, float* __restrict__ v_g,
       // that is not alive keeps its state
 #pragma clang fp contract(off)
       const bool my_alive = lt < 32 && (m ? aliveM : aliveP);
-      if (lt < 4 && my_alive) {
-        const float a = fclampf(act[lt], -1.0f, 1.0f);
-        const float vn = 0.8f * st[4 + lt] + a * 0.1f * 5.0f;
-        st[4 + lt] = vn;
-        st[lt] = fclampf(st[lt] + vn * 0.1f, -TAG_ARENA, TAG_ARENA);
-      }
+      if (lt < 4 && my_alive) tag_move(st[lt], st[4 + lt], act[lt]);
       __syncthreads();
       const float dxP = stP[0] - stP[2], dyP = stP[1] - stP[3];
       const float dP = sqrtf(dxP * dxP + dyP * dyP);
       const float dxM = stM[0] - stM[2], dyM = stM[1] - stM[3];
       const float dM = sqrtf(dxM * dxM + dyM * dyM);
-      const bool caughtP = dP < 0.3f, caughtM = dM < 0.3f;
+      const bool caughtP = dP < TAG_CATCH_DIST, caughtM = dM < TAG_CATCH_DIST;
       if (my_alive) {
-        const float d = m ? dM : dP;
-        const float bonus = (m ? caughtM : caughtP) ? 10.0f : 0.0f;
         if (lt == 0) {
-          rew[0] += -d + bonus;
-          rew[1] += d - bonus;
+          tag_reward(m ? dM : dP, m ? caughtM : caughtP, rew[0], rew[1]);
           steps[0] += 1.0f;
         }
         if (lt < 2 * TAG_OB) {
           // post-step observation of agent lt / 8, the terminal one included
-          const int i = lt >> 3, k = lt & 7;
-          const int who = (k & 4) ? 1 - i : i;
-          const double ob = (double)st[((k >> 1) & 1) * 4 + who * 2 + (k & 1)];
+          const double ob = (double)st[tag_ob_index(lt >> 3, lt & 7)];
           obsum[lt] += ob;
           obsq[lt] += ob * ob;
         }
@@ -437,14 +356,14 @@ extern "C" int es_tag_pair_episode(void* p, void* v, void* alive, void* steps,
                                    uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
                                    int32_t n_pairs, int32_t n_single, int32_t n_steps,
                                    int32_t act_final, int32_t noiseless_from, void* stream) {
-  if (n_agents != 2) return -112;
-  if (ob_dim != TAG_OB) return -110;
+  // the shared checks read a per-game call: theta_i as policy i's rows
+  const TagCall c{p, v, alive, steps, rew_total, ob_sum, ob_sumsq, theta0, theta1, obmean0,
+                  obmean1, obstd0, obstd1, dims0_host, ndims0, dims1_host, ndims1,
+                  row_stride0, row_stride1, ob_clip0, ob_clip1, ac_std_dev0, ac_std_dev1,
+                  seed_dev, salt_base, n_agents, ob_dim, 2 * n_pairs + n_single, n_steps,
+                  act_final, noiseless_from, stream};
   TagPolicy P0, P1;
-  int rc = tag_policy_init(&P0, false, theta0, obmean0, obstd0, ac_std_dev0, dims0_host,
-                           ndims0, row_stride0, ob_clip0);
-  if (rc) return rc;
-  rc = tag_policy_init(&P1, false, theta1, obmean1, obstd1, ac_std_dev1, dims1_host, ndims1,
-                       row_stride1, ob_clip1);
+  const int rc = tag_policies_init(c, false, &P0, &P1);
   if (rc) return rc;
   if (n_pairs < 0 || n_single < 0 || n_single > 1) return -113;
   if (n_pairs + n_single == 0 || n_steps <= 0) return 0;

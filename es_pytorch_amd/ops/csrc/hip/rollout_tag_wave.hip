@@ -31,10 +31,6 @@
 #include "tag_env.h"
 #include "wave_mlp.h"
 
-#define TGW_MAXW 64            // widest layer the lane mapping covers
-#define TGW_LDS_BUDGET 65536   // dynamic LDS of a block
-#define TGW_WAVES 4            // waves of a block
-
 struct TagWaveArgs {
   float *p, *v, *alive, *steps, *rew;  // (n, 2, 2) x2, (n), (n), (n, 2)
   double *obsum, *obsq;                // (n, 2, 8)
@@ -59,27 +55,12 @@ __device__ __forceinline__ float tgw_pick(const float (&st)[8], int idx) {
   return b2 ? hi : lo;
 }
 
-// Where observation k of agent i sits in st = p[2][2] v[2][2]: own p, own v,
-// other p, other v (the indexing of tag_agent_forward).
-__device__ __forceinline__ int tgw_ob_index(int i, int k) {
-  const int who = (k & 4) ? 1 - i : i;
-  return ((k >> 1) & 1) * 4 + who * 2 + (k & 1);
-}
-
 // BatchedPursuitTag.step on st with the raw actions act[agent][xy], op for op
 // in fp32 as tag_episode_kernel has it; returns the distance after the step.
 __device__ __forceinline__ float tgw_env_step(float (&st)[8], const float (&act)[4]) {
 #pragma clang fp contract(off)
-  auto move = [](float& p, float& v, float raw) {
-    const float a = fclampf(raw, -1.0f, 1.0f);
-    const float vn = 0.8f * v + a * 0.1f * 5.0f;
-    v = vn;
-    p = fclampf(p + vn * 0.1f, -TAG_ARENA, TAG_ARENA);
-  };
-  move(st[0], st[4], act[0]);
-  move(st[1], st[5], act[1]);
-  move(st[2], st[6], act[2]);
-  move(st[3], st[7], act[3]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tag_move(st[k], st[4 + k], act[k]);
   const float dx = st[0] - st[2], dy = st[1] - st[3];
   return sqrtf(dx * dx + dy * dy);
 }
@@ -131,13 +112,13 @@ tag_wave_episode_kernel(TagWaveArgs W) {
   // lane k < 8 owns observation k of either agent: its normalisation
   // (lanes >= 8 repeat observation k & 7; the forward reads lanes < 8 only)
   const int k8 = lane & 7;
-  const int ob_idx0 = tgw_ob_index(0, k8), ob_idx1 = tgw_ob_index(1, k8);
+  const int ob_idx0 = tag_ob_index(0, k8), ob_idx1 = tag_ob_index(1, k8);
   const float mean0 = W.P0.obmean[k8], std0 = W.P0.obstd[k8];
   const float mean1 = W.P1.obmean[k8], std1 = W.P1.obstd[k8];
   // lane l < 16 owns the moments of observation l & 7 of agent l >> 3
   // (lanes >= 16 repeat lane l & 15 and store nothing)
   const int l16 = lane & 15;
-  const int mom_idx = tgw_ob_index(l16 >> 3, k8);
+  const int mom_idx = tag_ob_index(l16 >> 3, k8);
   double obsum = W.obsum[(int64_t)b * 2 * TAG_OB + l16];
   double obsq = W.obsq[(int64_t)b * 2 * TAG_OB + l16];
   const uint64_t seed0 = W.seed_dev ? *W.seed_dev : 0;
@@ -156,14 +137,9 @@ tag_wave_episode_kernel(TagWaveArgs W) {
     const float act[4] = {clw_readlane(a0, 0), clw_readlane(a0, 1), clw_readlane(a1, 0),
                           clw_readlane(a1, 1)};
     const float d = tgw_env_step(st, act);
-    const bool caught = d < 0.3f;
-    {
-#pragma clang fp contract(off)
-      const float bonus = caught ? 10.0f : 0.0f;
-      rew0 += -d + bonus;
-      rew1 += d - bonus;
-      steps += 1.0f;
-    }
+    const bool caught = d < TAG_CATCH_DIST;
+    tag_reward(d, caught, rew0, rew1);
+    steps += 1.0f;
     // post-step observation, the terminal one included
     const double o = (double)tgw_pick(st, mom_idx);
     obsum += o;
@@ -189,86 +165,44 @@ tag_wave_episode_kernel(TagWaveArgs W) {
   }
 }
 
-// Coverage, the one place it is decided: 0 and the launch geometry, or -116.
-static inline int tag_wave_geometry(const MlpShape& s0, const MlpShape& s1, bool f32,
-                                    TagWaveArgs* W) {
-  int64_t n[2], bytes[2];
-  const MlpShape* sh[2] = {&s0, &s1};
-  for (int i = 0; i < 2; ++i) {
-    for (int l = 0; l <= sh[i]->n_layers; ++l)
-      if (sh[i]->dims[l] > TGW_MAXW) return -116;
-    n[i] = sh[i]->boff[sh[i]->n_layers - 1] + sh[i]->dims[sh[i]->n_layers];
-    bytes[i] = (n[i] * (f32 ? 4 : 2) + 15) & ~(int64_t)15;
-  }
-  const int64_t region = bytes[0] + bytes[1];
-  if (region > TGW_LDS_BUDGET) return -116;
-  W->gpb = 4 * region <= TGW_LDS_BUDGET ? 4 : 2 * region <= TGW_LDS_BUDGET ? 2 : 1;
-  W->region_bytes = (int)region;
-  W->row1_bytes = (int)bytes[0];
-  W->n0 = (int)n[0];
-  W->n1 = (int)n[1];
-  return 0;
+// The shared checks (tag_policies_init), then the coverage: fills the policies
+// and the geometry of W.
+static inline int tag_wave_init(TagWaveArgs* W, bool f32, const TagCall& c) {
+  const int rc = tag_policies_init(c, f32, &W->P0, &W->P1);
+  if (rc) return rc;
+  W->n0 = wave_row_elems(W->P0.sh);
+  W->n1 = wave_row_elems(W->P1.sh);
+  if (W->n0 < 0 || W->n1 < 0) return -116;
+  W->row1_bytes = wave_row_bytes(W->n0, f32);
+  W->region_bytes = W->row1_bytes + wave_row_bytes(W->n1, f32);
+  W->gpb = wave_regions_per_block(W->region_bytes);
+  return W->gpb < 0 ? W->gpb : 0;
 }
 
-// The checks of tag_launch in its order, then the coverage.
-static inline int tag_wave_init(TagWaveArgs* W, bool f32, const void* weights0,
-                                const void* weights1, const void* obmean0,
-                                const void* obmean1, const void* obstd0, const void* obstd1,
-                                const int32_t* dims0_host, int32_t ndims0,
-                                const int32_t* dims1_host, int32_t ndims1,
-                                int64_t row_stride0, int64_t row_stride1, float ob_clip0,
-                                float ob_clip1, const void* ac_std_dev0,
-                                const void* ac_std_dev1, int32_t n_agents, int32_t ob_dim) {
-  if (n_agents != 2) return -112;
-  if (ob_dim != TAG_OB) return -110;
-  int rc = tag_policy_init(&W->P0, f32, weights0, obmean0, obstd0, ac_std_dev0, dims0_host,
-                           ndims0, row_stride0, ob_clip0);
-  if (rc) return rc;
-  rc = tag_policy_init(&W->P1, f32, weights1, obmean1, obstd1, ac_std_dev1, dims1_host,
-                       ndims1, row_stride1, ob_clip1);
-  if (rc) return rc;
-  return tag_wave_geometry(W->P0.sh, W->P1.sh, f32, W);
-}
-
-static inline int tag_wave_launch(bool f32, void* p, void* v, void* alive, void* steps,
-                                  void* rew_total, void* ob_sum, void* ob_sumsq,
-                                  const void* weights0, const void* weights1,
-                                  const void* obmean0, const void* obmean1,
-                                  const void* obstd0, const void* obstd1,
-                                  const int32_t* dims0_host, int32_t ndims0,
-                                  const int32_t* dims1_host, int32_t ndims1,
-                                  int64_t row_stride0, int64_t row_stride1, float ob_clip0,
-                                  float ob_clip1, const void* ac_std_dev0,
-                                  const void* ac_std_dev1, const void* seed_dev,
-                                  uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
-                                  int32_t n_games, int32_t n_steps, int32_t act_final,
-                                  int32_t noiseless_from, void* stream) {
+static inline int tag_wave_launch(bool f32, const TagCall& c) {
   TagWaveArgs W;
-  const int rc = tag_wave_init(&W, f32, weights0, weights1, obmean0, obmean1, obstd0, obstd1,
-                               dims0_host, ndims0, dims1_host, ndims1, row_stride0,
-                               row_stride1, ob_clip0, ob_clip1, ac_std_dev0, ac_std_dev1,
-                               n_agents, ob_dim);
+  const int rc = tag_wave_init(&W, f32, c);
   if (rc) return rc;
-  if (n_games <= 0 || n_steps <= 0) return 0;
-  W.p = (float*)p;
-  W.v = (float*)v;
-  W.alive = (float*)alive;
-  W.steps = (float*)steps;
-  W.rew = (float*)rew_total;
-  W.obsum = (double*)ob_sum;
-  W.obsq = (double*)ob_sumsq;
-  W.seed_dev = (const uint64_t*)seed_dev;
-  W.salt_base = salt_base;
-  W.n_games = n_games;
-  W.n_steps = n_steps;
-  W.act_final = act_final;
-  W.noiseless_from = noiseless_from;
-  const dim3 grid((unsigned)((n_games + W.gpb - 1) / W.gpb)), block(64 * TGW_WAVES);
+  if (c.n_games <= 0 || c.n_steps <= 0) return 0;
+  W.p = (float*)c.p;
+  W.v = (float*)c.v;
+  W.alive = (float*)c.alive;
+  W.steps = (float*)c.steps;
+  W.rew = (float*)c.rew_total;
+  W.obsum = (double*)c.ob_sum;
+  W.obsq = (double*)c.ob_sumsq;
+  W.seed_dev = (const uint64_t*)c.seed_dev;
+  W.salt_base = c.salt_base;
+  W.n_games = c.n_games;
+  W.n_steps = c.n_steps;
+  W.act_final = c.act_final;
+  W.noiseless_from = c.noiseless_from;
+  const dim3 grid((unsigned)((c.n_games + W.gpb - 1) / W.gpb)), block(64 * WAVE_WAVES);
   const unsigned lds = (unsigned)(W.gpb * W.region_bytes);
   if (f32)
-    tag_wave_episode_kernel<float><<<grid, block, lds, (hipStream_t)stream>>>(W);
+    tag_wave_episode_kernel<float><<<grid, block, lds, (hipStream_t)c.stream>>>(W);
   else
-    tag_wave_episode_kernel<uint16_t><<<grid, block, lds, (hipStream_t)stream>>>(W);
+    tag_wave_episode_kernel<uint16_t><<<grid, block, lds, (hipStream_t)c.stream>>>(W);
   ES_CHECK_LAUNCH();
   return 0;
 }
@@ -278,51 +212,19 @@ static inline int tag_wave_launch(bool f32, void* p, void* v, void* alive, void*
 extern "C" int es_tag_wave_check(const int32_t* dims0_host, int32_t ndims0,
                                  const int32_t* dims1_host, int32_t ndims1,
                                  int64_t row_stride0, int64_t row_stride1, int32_t f32) {
+  TagCall c{};
+  c.dims0_host = dims0_host;
+  c.ndims0 = ndims0;
+  c.dims1_host = dims1_host;
+  c.ndims1 = ndims1;
+  c.row_stride0 = row_stride0;
+  c.row_stride1 = row_stride1;
+  c.n_agents = 2;
+  c.ob_dim = TAG_OB;
   TagWaveArgs W;
-  return tag_wave_init(&W, f32 != 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       dims0_host, ndims0, dims1_host, ndims1, row_stride0, row_stride1, 0.0f,
-                       0.0f, nullptr, nullptr, 2, TAG_OB);
+  return tag_wave_init(&W, f32 != 0, c);
 }
 
-// Argument list and contract of es_tag_episode (rollout_tag.hip).
-extern "C" int es_tag_wave_episode(void* p, void* v, void* alive, void* steps,
-                                   void* rew_total, void* ob_sum, void* ob_sumsq,
-                                   const void* weights0, const void* weights1,
-                                   const void* obmean0, const void* obmean1,
-                                   const void* obstd0, const void* obstd1,
-                                   const int32_t* dims0_host, int32_t ndims0,
-                                   const int32_t* dims1_host, int32_t ndims1,
-                                   int64_t row_stride0, int64_t row_stride1, float ob_clip0,
-                                   float ob_clip1, const void* ac_std_dev0,
-                                   const void* ac_std_dev1, const void* seed_dev,
-                                   uint64_t salt_base, int32_t n_agents, int32_t ob_dim,
-                                   int32_t n_games, int32_t n_steps, int32_t act_final,
-                                   int32_t noiseless_from, void* stream) {
-  return tag_wave_launch(false, p, v, alive, steps, rew_total, ob_sum, ob_sumsq, weights0,
-                         weights1, obmean0, obmean1, obstd0, obstd1, dims0_host, ndims0,
-                         dims1_host, ndims1, row_stride0, row_stride1, ob_clip0, ob_clip1,
-                         ac_std_dev0, ac_std_dev1, seed_dev, salt_base, n_agents, ob_dim,
-                         n_games, n_steps, act_final, noiseless_from, stream);
-}
-
-// fp32 rows: same argument list; weights_i is float32 (n_games, row_stride_i).
-extern "C" int es_tag_wave_episode_f32(void* p, void* v, void* alive, void* steps,
-                                       void* rew_total, void* ob_sum, void* ob_sumsq,
-                                       const void* weights0, const void* weights1,
-                                       const void* obmean0, const void* obmean1,
-                                       const void* obstd0, const void* obstd1,
-                                       const int32_t* dims0_host, int32_t ndims0,
-                                       const int32_t* dims1_host, int32_t ndims1,
-                                       int64_t row_stride0, int64_t row_stride1,
-                                       float ob_clip0, float ob_clip1,
-                                       const void* ac_std_dev0, const void* ac_std_dev1,
-                                       const void* seed_dev, uint64_t salt_base,
-                                       int32_t n_agents, int32_t ob_dim, int32_t n_games,
-                                       int32_t n_steps, int32_t act_final,
-                                       int32_t noiseless_from, void* stream) {
-  return tag_wave_launch(true, p, v, alive, steps, rew_total, ob_sum, ob_sumsq, weights0,
-                         weights1, obmean0, obmean1, obstd0, obstd1, dims0_host, ndims0,
-                         dims1_host, ndims1, row_stride0, row_stride1, ob_clip0, ob_clip1,
-                         ac_std_dev0, ac_std_dev1, seed_dev, salt_base, n_agents, ob_dim,
-                         n_games, n_steps, act_final, noiseless_from, stream);
-}
+// Argument list and contract: TAG_EPISODE_ENTRY (tag_env.h).
+TAG_EPISODE_ENTRY(es_tag_wave_episode, tag_wave_launch, false)
+TAG_EPISODE_ENTRY(es_tag_wave_episode_f32, tag_wave_launch, true)

@@ -1,9 +1,34 @@
-// The wave-per-slot kernels' forward (rollout_classic_wave.hip,
-// rollout_tag_wave.hip): a weight row copied into a wave's own LDS region
-// and an MLP of layers at most 64 wide walked inside the wave, activations
-// in registers.
+// What the wave-per-slot kernels share (rollout_classic_wave.hip,
+// rollout_tag_wave.hip): the launch geometry and what it covers, a weight row
+// copied into a wave's own LDS region and an MLP of layers at most 64 wide
+// walked inside the wave, activations in registers.
 #pragma once
 #include "mlp_core.h"
+
+#define WAVE_MAXW 64           // widest layer the lane mapping covers
+#define WAVE_LDS_BUDGET 65536  // dynamic LDS of a block
+#define WAVE_WAVES 4           // waves of a block
+
+// Coverage, the one place it is decided. A wave's LDS region holds its rows,
+// each padded to 16 B; a block holds the regions of 4, 2 or 1 waves.
+//
+// Elements of a row of sh, or -116 where a layer is wider than WAVE_MAXW.
+static inline int wave_row_elems(const MlpShape& sh) {
+  for (int l = 0; l <= sh.n_layers; ++l)
+    if (sh.dims[l] > WAVE_MAXW) return -116;
+  return (int)(sh.boff[sh.n_layers - 1] + sh.dims[sh.n_layers]);
+}
+
+static inline int wave_row_bytes(int n_elems, bool f32) {
+  return (n_elems * (f32 ? 4 : 2) + 15) & ~15;
+}
+
+// Regions of region_bytes a block runs (the most that fit WAVE_LDS_BUDGET), or
+// -116 where one alone does not fit.
+static inline int wave_regions_per_block(int region_bytes) {
+  if (region_bytes > WAVE_LDS_BUDGET) return -116;
+  return 4 * region_bytes <= WAVE_LDS_BUDGET ? 4 : 2 * region_bytes <= WAVE_LDS_BUDGET ? 2 : 1;
+}
 
 // Keeps the compiler from pairing the lanes' scalar fp32 operations into
 // packed ones in these kernels.

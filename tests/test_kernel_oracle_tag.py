@@ -29,14 +29,10 @@ import torch
 
 from tests.oracle64 import ERR_FACTOR, fp32_error_scale, max_ratio
 from tests.oracle64_tag import TAG_KEYS, tag_rollout, tag_state
-from tests.test_kernel_oracle_mlp import bf16_tensor, make_net
+from tests.tag_harness import FLOAT_KEYS, MARGIN_MIN, NOISE, DeviceGame, check, make_starts
+from tests.test_kernel_oracle_mlp import make_net
 
 pytestmark = pytest.mark.gpu
-
-MARGIN_MIN = 1e-3
-N_CLOSE = 4                               # games 0..3 start close
-CLOSE_DIST = (0.2, 0.4, 0.6, 0.8)         # runner's distance from the chaser
-FLOAT_KEYS = ("p", "v", "rew_total", "ob_sum", "ob_sumsq")
 
 # name -> (dims0, dims1, games, steps, (stride_pad0, stride_pad1),
 #          (ob_clip0, ob_clip1), rng seed)
@@ -45,30 +41,11 @@ CASES = {
     "asymmetric": ([8, 16, 2], [8, 32, 32, 2], 9, 12, (0, 8), (5.0, 1.5), 6),
     "flagship_width": ([8, 256, 256, 2], [8, 256, 256, 2], 5, 6, (0, 0), (5.0, 5.0), 3),
 }
-NOISE = dict(seed=20240607, ac_std=(0.05, 0.05), noiseless_from=8)
 
 
 @pytest.fixture(scope="module")
 def dev():
     return torch.device("cuda", 0)
-
-
-def make_starts(rng, B):
-    """p (B, 2, 2): games 0..3 with the runner CLOSE_DIST from the chaser in a
-    random direction, the others at least 1.5 apart, all within +-2.5."""
-    p = np.zeros((B, 2, 2), dtype=np.float32)
-    for b in range(B):
-        while True:
-            c = rng.uniform(-2.0, 2.0, size=2)
-            if b < N_CLOSE:
-                th = rng.uniform(0, 2 * np.pi)
-                r = c + CLOSE_DIST[b] * np.array([np.cos(th), np.sin(th)])
-            else:
-                r = rng.uniform(-2.5, 2.5, size=2)
-            if np.abs(r).max() <= 2.5 and (b < N_CLOSE or np.linalg.norm(r - c) >= 1.5):
-                break
-        p[b, 0], p[b, 1] = c, r
-    return p
 
 
 def build_case(name):
@@ -108,78 +85,11 @@ def oracle(name, noise=None):
     return _ORACLE[key]
 
 
-class DeviceGame:
-    """Device copies of a case: state with one NaN guard row, both nets."""
-
-    def __init__(self, dev, c, noise=None):
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        self.dev, self.B = dev, c["B"]
-        self.state = {}
-        for k in TAG_KEYS:
-            a = np.asarray(c["state"][k])
-            g = np.full((1,) + a.shape[1:], np.nan, dtype=a.dtype)
-            self.state[k] = t(np.concatenate([a, g], axis=0))
-        self.nets = []
-        for n in c["dev_nets"]:
-            self.nets.append(dict(w=bf16_tensor(n["wbits"], dev), mean=t(n["obmean"]),
-                                  std=t(n["obstd"]), stride=n["stride"],
-                                  dims=np.array(n["dims"], dtype=np.int32),
-                                  clip=n["ob_clip"]))
-        self.seed = self.acstd = None
-        self.noiseless_from = 0
-        if noise is not None:
-            self.seed = t(np.array([noise["seed"]], np.int64))
-            self.acstd = [t(np.array([s], np.float32)) for s in noise["ac_std"]]
-            self.noiseless_from = noise["noiseless_from"]
-
-    def launch(self, n_steps, salt_base=0, n_games=None, n_agents=2, ob_dim=8):
-        from es_pytorch_amd import ops
-        s, (n0, n1) = self.state, self.nets
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        rc = ops.hip().es_tag_episode(
-            s["p"].data_ptr(), s["v"].data_ptr(), s["alive"].data_ptr(),
-            s["steps"].data_ptr(), s["rew_total"].data_ptr(), s["ob_sum"].data_ptr(),
-            s["ob_sumsq"].data_ptr(), n0["w"].data_ptr(), n1["w"].data_ptr(),
-            n0["mean"].data_ptr(), n1["mean"].data_ptr(), n0["std"].data_ptr(),
-            n1["std"].data_ptr(), n0["dims"].ctypes.data, len(n0["dims"]),
-            n1["dims"].ctypes.data, len(n1["dims"]), n0["stride"], n1["stride"],
-            n0["clip"], n1["clip"], ptr(self.acstd[0] if self.acstd else None),
-            ptr(self.acstd[1] if self.acstd else None), ptr(self.seed), salt_base,
-            n_agents, ob_dim, self.B if n_games is None else n_games, n_steps, 1,
-            self.noiseless_from, torch.cuda.current_stream(self.dev).cuda_stream)
-        torch.cuda.synchronize(self.dev)
-        return rc
-
-    def read(self):
-        """Host copy of the B games; the guard row must still be NaN."""
-        out = {}
-        for k, v in self.state.items():
-            a = v.cpu().numpy()
-            assert np.isnan(a[self.B:]).all(), f"{k}: guard row written"
-            out[k] = a[:self.B]
-        return out
-
-
 def run_case(dev, name, noise=None):
     c = build_case(name)
     g = DeviceGame(dev, c, noise)
     assert g.launch(c["n_steps"]) == 0
     return g.read()
-
-
-def check(name, got, y64, e32, games=slice(None)):
-    assert np.array_equal(got["steps"][games], y64["steps"][games]), name
-    assert np.array_equal(got["alive"][games], y64["alive"][games]), name
-    worst = (0.0, "")
-    for k in FLOAT_KEYS:
-        assert np.isfinite(got[k]).all(), (name, k)
-        r = max_ratio(got[k][games], y64[k][games], e32[k])
-        print(f"ORACLE-RATIO tag {name} {k} ratio={r:.2f} E32={e32[k]:.3g}")
-        worst = max(worst, (r, k))
-    print(f"ORACLE-RATIO tag {name} worst ratio={worst[0]:.2f} ({worst[1]})")
-    for k in FLOAT_KEYS:
-        r = max_ratio(got[k][games], y64[k][games], e32[k])
-        assert r <= ERR_FACTOR, (name, k, r, e32[k])
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -1,6 +1,7 @@
 """es_tag_episode_f32 against the float64 oracle (tests/oracle64_tag.py).
 
-The fp32-rows twin of tests/test_kernel_oracle_tag.py, whose helpers it uses:
+The fp32-rows twin of tests/test_kernel_oracle_tag.py, on the helpers of
+tests/tag_harness.py:
 direct calls on test-owned buffers, ``|kernel - oracle64| <= 16 * E32`` per
 state buffer (E32: the same rollout in numpy float32), ``steps`` and ``alive``
 exact, one NaN guard row behind every state buffer. The weight blobs are drawn
@@ -39,8 +40,8 @@ import torch
 
 from tests.oracle64 import ERR_FACTOR, f32_to_bf16_bits, fp32_error_scale, max_ratio, n_params
 from tests.oracle64_tag import TAG_KEYS, tag_rollout, tag_state
-from tests.test_kernel_oracle_tag import (FLOAT_KEYS, MARGIN_MIN, NOISE, DeviceGame, check,
-                                          make_starts)
+from tests.tag_harness import (FLOAT_KEYS, MARGIN_MIN, NOISE, DeviceGame, check, make_net_f32,
+                               make_starts)
 
 pytestmark = pytest.mark.gpu
 
@@ -57,21 +58,6 @@ CASES = {
 @pytest.fixture(scope="module")
 def dev():
     return torch.device("cuda", 0)
-
-
-def make_net_f32(rng, dims, rows, stride_pad=0):
-    """make_net's blob (rows + 1 rows, the same draws and scales) with the
-    float32 values kept as they are; returns (float32 array, stride)."""
-    n = n_params(dims)
-    stride = (n + 7) // 8 * 8 + stride_pad
-    w = np.zeros((rows + 1, stride), dtype=np.float32)
-    off = 0
-    for I, O in zip(dims[:-1], dims[1:]):
-        w[:, off:off + I * O] = rng.randn(rows + 1, I * O) * (0.7 / np.sqrt(I))
-        off += I * O
-        w[:, off:off + O] = rng.randn(rows + 1, O) * 0.1
-        off += O
-    return w, stride
 
 
 def build_case(name):
@@ -116,27 +102,11 @@ class DeviceGameF32(DeviceGame):
 
     def __init__(self, dev, c, noise=None):
         super().__init__(dev, c, noise)
-        for net, n in zip(self.nets, c["dev_nets"]):
-            net["w"] = torch.from_numpy(np.ascontiguousarray(n["w32"])).to(dev)
-            assert net["w"].dtype == torch.float32
+        self.use_f32_blobs(c)
 
-    def launch(self, n_steps, salt_base=0, n_games=None, n_agents=2, ob_dim=8):
+    def entry(self):
         from es_pytorch_amd import ops
-        s, (n0, n1) = self.state, self.nets
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        rc = ops.hip().es_tag_episode_f32(
-            s["p"].data_ptr(), s["v"].data_ptr(), s["alive"].data_ptr(),
-            s["steps"].data_ptr(), s["rew_total"].data_ptr(), s["ob_sum"].data_ptr(),
-            s["ob_sumsq"].data_ptr(), n0["w"].data_ptr(), n1["w"].data_ptr(),
-            n0["mean"].data_ptr(), n1["mean"].data_ptr(), n0["std"].data_ptr(),
-            n1["std"].data_ptr(), n0["dims"].ctypes.data, len(n0["dims"]),
-            n1["dims"].ctypes.data, len(n1["dims"]), n0["stride"], n1["stride"],
-            n0["clip"], n1["clip"], ptr(self.acstd[0] if self.acstd else None),
-            ptr(self.acstd[1] if self.acstd else None), ptr(self.seed), salt_base,
-            n_agents, ob_dim, self.B if n_games is None else n_games, n_steps, 1,
-            self.noiseless_from, torch.cuda.current_stream(self.dev).cuda_stream)
-        torch.cuda.synchronize(self.dev)
-        return rc
+        return ops.hip().es_tag_episode_f32
 
 
 def run_case(dev, name, noise=None):

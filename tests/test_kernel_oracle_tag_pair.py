@@ -1,6 +1,7 @@
 """es_tag_pair_episode against the float64 oracle (tests/oracle64_tag.py).
 
-The pair form of tests/test_kernel_oracle_tag.py, whose helpers it uses: direct
+The pair form of tests/test_kernel_oracle_tag.py, on the helpers of
+tests/tag_harness.py: direct
 calls on test-owned buffers, ``|kernel - oracle64| <= 16 * E32`` per float
 state buffer (E32: the same rollout in numpy float32), ``steps`` and ``alive``
 exact, one NaN guard row behind every state buffer, which must still be NaN
@@ -50,8 +51,8 @@ import torch
 from tests.oracle64 import (ERR_FACTOR, bf16_bits_to_f64, f32_to_bf16_bits, fp32_error_scale,
                             max_ratio, n_params)
 from tests.oracle64_tag import TAG_KEYS, tag_rollout, tag_state
+from tests.tag_harness import FLOAT_KEYS, MARGIN_MIN, DeviceGame, check
 from tests.test_kernel_oracle_mlp import bf16_tensor
-from tests.test_kernel_oracle_tag import FLOAT_KEYS, MARGIN_MIN, DeviceGame, check
 
 pytestmark = pytest.mark.gpu
 

@@ -2,7 +2,7 @@
 member rows in LDS, policies at most 64 wide) against the float64 oracle, with
 the bound (``|kernel - oracle64| <= 16 * E32`` per float buffer, ``steps`` and
 ``alive`` exact, NaN guard row intact) and the helpers of
-tests/test_kernel_oracle_tag.py and its fp32 twin. The blobs are drawn as
+tests/tag_harness.py. The blobs are drawn as
 ``make_net_f32`` draws them; the bf16 rows are those values rounded. Every case
 has 9 games and 12 steps, so the last block is partly empty at 4, 2 and 1 games
 per block (wide64: 2 on bf16, 1 on fp32). Every oracle asserts, cap zero, that
@@ -24,8 +24,8 @@ import torch
 from es_pytorch_amd import ops
 from tests.oracle64 import bf16_bits_to_f64, f32_to_bf16_bits, fp32_error_scale
 from tests.oracle64_tag import TAG_KEYS, tag_rollout, tag_state
-from tests.test_kernel_oracle_tag import MARGIN_MIN, NOISE, DeviceGame, check, make_starts
-from tests.test_kernel_oracle_tag_f32 import make_net_f32
+from tests.tag_harness import (MARGIN_MIN, NOISE, DeviceGame, check, make_net_f32,
+                               make_starts)
 
 pytestmark = pytest.mark.gpu
 dev = torch.device("cuda", 0)
@@ -83,29 +83,11 @@ class WaveGame(DeviceGame):
     def __init__(self, dev, c, noise=None):
         super().__init__(dev, c, noise)
         self.f32 = c["f32"]
-        for net, n in zip(self.nets, c["dev_nets"] if self.f32 else []):
-            net["w"] = torch.from_numpy(np.ascontiguousarray(n["w32"])).to(dev)
+        if self.f32:
+            self.use_f32_blobs(c)
 
-    def args(self, n_steps, salt_base=0, n_games=None, n_agents=2, ob_dim=8):
-        s, (n0, n1) = self.state, self.nets
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        return (
-            s["p"].data_ptr(), s["v"].data_ptr(), s["alive"].data_ptr(),
-            s["steps"].data_ptr(), s["rew_total"].data_ptr(), s["ob_sum"].data_ptr(),
-            s["ob_sumsq"].data_ptr(), n0["w"].data_ptr(), n1["w"].data_ptr(),
-            n0["mean"].data_ptr(), n1["mean"].data_ptr(), n0["std"].data_ptr(),
-            n1["std"].data_ptr(), n0["dims"].ctypes.data, len(n0["dims"]),
-            n1["dims"].ctypes.data, len(n1["dims"]), n0["stride"], n1["stride"],
-            n0["clip"], n1["clip"], ptr(self.acstd[0] if self.acstd else None),
-            ptr(self.acstd[1] if self.acstd else None), ptr(self.seed), salt_base,
-            n_agents, ob_dim, self.B if n_games is None else n_games, n_steps, 1,
-            self.noiseless_from, torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def launch(self, *a, **kw):
-        fn = ops.hip().es_tag_wave_episode_f32 if self.f32 else ops.hip().es_tag_wave_episode
-        rc = fn(*self.args(*a, **kw))
-        torch.cuda.synchronize(self.dev)
-        return rc
+    def entry(self):
+        return ops.hip().es_tag_wave_episode_f32 if self.f32 else ops.hip().es_tag_wave_episode
 
     def shape_check(self):
         n0, n1 = self.nets

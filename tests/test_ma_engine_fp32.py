@@ -37,9 +37,9 @@ import torch
 from tests.oracle64 import ERR_FACTOR, fp32_error_scale, max_ratio
 from tests.oracle64_f32 import fp32_member_rows
 from tests.oracle64_tag import tag_rollout, tag_state
+from tests.tag_harness import MARGIN_MIN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MARGIN_MIN = 1e-3
 MAX_STEPS = 40
 PPG = 16
 SEEDS = (1, 2)              # torch.manual_seed (policy init), engine RandomState

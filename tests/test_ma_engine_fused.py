@@ -18,10 +18,10 @@ import torch
 
 from tests.oracle64 import ERR_FACTOR, bf16_bits_to_f64, fp32_error_scale, max_ratio
 from tests.oracle64_tag import tag_rollout, tag_state
+from tests.tag_harness import MARGIN_MIN
 
 pytestmark = pytest.mark.gpu
 
-MARGIN_MIN = 1e-3
 MAX_STEPS = 40
 PPG = 16
 SEEDS = (1, 2)              # torch.manual_seed (policy init), engine RandomState

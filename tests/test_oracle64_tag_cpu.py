@@ -14,7 +14,8 @@ import torch
 
 from es_pytorch_amd.envs.multiagent import BatchedPursuitTag
 from tests.oracle64_tag import TAG_KEYS, tag_rollout, tag_state
-from tests.test_kernel_oracle_tag import MARGIN_MIN, NOISE, build_case
+from tests.tag_harness import MARGIN_MIN, NOISE
+from tests.test_kernel_oracle_tag import build_case
 
 EPS32 = 2.0 ** -23
 ULPS = 4.0
