@@ -26,6 +26,8 @@ One rank = one GPU; per generation:
    (``rollout_classic.hip``), ended slots leaving the kernel's loop;
    ``classic_wave`` (opt-in, nets at most 64 wide) gives each slot a
    wavefront instead of a workgroup (``rollout_classic_wave.hip``);
+   ``loco_wave`` (opt-in, state and nets at most 64 wide) does the same for
+   the locomotion envs, all slots in one launch (``rollout_loco_wave.hip``);
 4. (fit+, fit-, idx) fp64 triples go through ONE RCCL all_gather over xGMI
    (replaces the replicated Alltoall, ``es.py:84-95``); ranking runs
    redundantly on every rank (reference README.md:10-12 — parameters are
@@ -103,7 +105,8 @@ class GpuEngine:
                  eps_fp8: Optional[bool] = None,
                  weights_dtype: Optional[str] = None,
                  classic_fused: Optional[bool] = None,
-                 classic_wave: Optional[bool] = None):
+                 classic_wave: Optional[bool] = None,
+                 loco_wave: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -135,6 +138,34 @@ class GpuEngine:
                 print(f"[engine] weights_dtype=fp32: ignoring {', '.join(ignored)} "
                       f"from the config (no fp32 variant)", file=sys.stderr)
             pair_rollout = eps_fp8 = split_dyn = False
+        # loco_wave (opt-in): the wave-per-slot whole-episode kernel for the
+        # small locomotion envs and nets (rollout_loco_wave.hip), all B slots
+        # in one launch per generation. Per-member rows of either dtype; no
+        # pair / fp8 / split form. Never chosen by size, never a fallback.
+        if loco_wave is None:
+            loco_wave = cfg.general.get("loco_wave", False)
+        if not isinstance(loco_wave, bool):
+            raise ValueError(f"loco_wave must be true or false, got {loco_wave!r}")
+        self.loco_wave = loco_wave
+        if loco_wave:
+            for flag, val in (("pair_rollout", pair_rollout), ("eps_fp8", eps_fp8),
+                              ("split_dyn", split_dyn)):
+                if val is True:
+                    raise ValueError(
+                        f"{flag}=True is not available with loco_wave=True (the wave "
+                        f"kernel runs per-member rows only)")
+            if int(cfg.general.get("steps_per_launch", None) or 1) > 1:
+                raise ValueError(
+                    "loco_wave plays the whole episode in one launch; remove "
+                    "steps_per_launch from the config or leave loco_wave off")
+            ignored = [k for k in ("pair_rollout", "eps_fp8", "split_dyn")
+                       if bool(cfg.general.get(k, False))]
+            if ignored and not self.fp32 and comm.rank == 0:
+                import sys
+                print(f"[engine] loco_wave: ignoring {', '.join(ignored)} from the "
+                      f"config (no wave variant)", file=sys.stderr)
+            pair_rollout = eps_fp8 = split_dyn = False
+            self.rollout_mode = "episode"
         # steps per launch in "step" mode: k>1 runs k consecutive env steps
         # per kernel launch (bounded block drift, fewer launch boundaries)
         # A value in the config is honoured as given (1 = one launch per
@@ -338,6 +369,8 @@ class GpuEngine:
             self._zeros_n = torch.zeros(self.n, dtype=torch.float32, device=d)
             self._one_signs = torch.ones(self.pairs, dtype=torch.float32, device=d)
         self._warned_host_ranker = False
+        if self.loco_wave:
+            self._loco_wave_check()
 
         # whole-episode kernel for the classic-control envs (rollout_classic.hip):
         # ONE launch per generation instead of max_steps x (forward + a dozen
@@ -384,6 +417,32 @@ class GpuEngine:
                 "FFIntegGausAction* policy)")
         self._classic_kind = 0 if isinstance(env, BatchedCartPole) else 1
 
+    def _loco_wave_check(self):
+        """loco_wave=True on something the kernel does not cover fails here, at
+        construction (the shape rule lives in es_loco_wave_check alone)."""
+        from es_pytorch_amd.envs.locomotion import SyntheticLocomotion
+        env = self.env
+        if not (self.fused and isinstance(env, SyntheticLocomotion)
+                and self.device.type == "cuda"):
+            raise ValueError(
+                f"loco_wave runs the fused locomotion path: it needs a "
+                f"SyntheticLocomotion env on a GPU and fused left on, got "
+                f"{type(env).__name__} on {self.device.type} with fused={self.fused}")
+        lib = ops.hip()
+        if not hasattr(lib, "es_loco_wave_episode"):
+            raise RuntimeError(
+                "loco_wave=True needs es_loco_wave_episode, which the loaded HIP "
+                "library does not have (an earlier revision through ES_HIP_SO?)")
+        rc = lib.es_loco_wave_check(self.dims_arr.ctypes.data, len(self.dims_arr),
+                                    self.row_stride, env.sdim, env.ac_dim,
+                                    int(env.goal_conditioned), int(self.fp32))
+        if rc != 0:
+            raise ValueError(
+                f"loco_wave covers envs whose state and nets whose layers are all at "
+                f"most 64 wide and whose parameter row fits 64 KB of LDS beside the "
+                f"env's matrices; got state dim {env.sdim} and widths {list(self.dims)} "
+                f"(es_loco_wave_check returned {rc})")
+
     def _classic_wave_check(self):
         """The wave kernel's own coverage, asked of the library (the rule
         lives in es_classic_wave_check alone)."""
@@ -429,7 +488,8 @@ class GpuEngine:
         if self.pair_rollout:
             path, enc = "pair", "e4m3" if self.eps_fp8 else "bf16"
         else:
-            path = "split" if self.split_dyn else "fused" if self.fused else \
+            path = "split" if self.split_dyn else \
+                "loco_wave" if self.loco_wave else "fused" if self.fused else \
                 "classic_wave" if self.classic_wave else \
                 "classic" if self.classic_fused else "generic"
             enc = "none"
@@ -575,6 +635,29 @@ class GpuEngine:
             float(env.fall_threshold), float(env.dt), int(block_threads),
             self._stream()), name)
 
+    def _loco_wave_episode(self):
+        """The whole episode of all B slots in ONE launch of the wave-per-slot
+        kernel; the noiseless slots read row M - 1 of self.weights."""
+        env = self.env
+        goal_ptr = env.goal.data_ptr() if env.goal_conditioned else None
+        name = "es_loco_wave_episode" + ("_f32" if self.fp32 else "")
+        ops.check(getattr(ops.hip(), name)(
+            self.weights.data_ptr(), self.obmean.data_ptr(), self.obstd.data_ptr(),
+            self.dims_arr.ctypes.data, len(self.dims_arr), self.seed_dev.data_ptr(),
+            self.max_steps, float(self.policy._module.ob_clip),
+            self.acstd_dev.data_ptr(), self.row_stride,
+            env.s.data_ptr(), env.pos.data_ptr(), goal_ptr,
+            env.A_bf16.data_ptr(), env.B.data_ptr(), env.b0.data_ptr(),
+            env.wv.data_ptr(), env.wa.data_ptr(), env.wy.data_ptr(), env.wh.data_ptr(),
+            self.alive.data_ptr(), self.rew_total.data_ptr(),
+            self.member_steps.data_ptr(), self.behv.data_ptr(),
+            self.mo_sum.data_ptr(), self.mo_sumsq.data_ptr(),
+            0, self.B, 0, 0, env.sdim, env.ac_dim,
+            int(env.goal_conditioned), int(env.terminate_on_fall),
+            (self.M - 1) * self.eps, self.bins, self.eps, self.act_mode,
+            float(env.leak), float(env.ctrl_cost), float(env.alive_bonus),
+            float(env.fall_threshold), float(env.dt), self._stream()), name)
+
     def _loco_pair_episode(self, n_steps: Optional[int] = None, salt_base: int = 0):
         """n_steps consecutive env steps for every (pair, episode) block in
         ONE launch (default: the whole episode). Blocks never rendezvous, so
@@ -665,6 +748,9 @@ class GpuEngine:
         if self.classic_fused:
             self._classic_episode()
             return
+        if self.loco_wave:
+            self._loco_wave_episode()
+            return
         if self.fused and self.rollout_mode == "episode":
             # whole generation in one (+1 side) launch: every block runs its
             # member's full episode, blocks drift freely (no per-step
@@ -706,8 +792,8 @@ class GpuEngine:
 
     def _rollout(self):
         body = self._loco_step if self.fused else self._step_body
-        # classic_fused: one launch, nothing for a hipGraph to save
-        if self.use_graph and not self.classic_fused:
+        # classic_fused, loco_wave: one launch, nothing for a hipGraph to save
+        if self.use_graph and not self.classic_fused and not self.loco_wave:
             if self._graph is None:
                 # warmup (lazy inits must happen outside capture), then capture once
                 s = torch.cuda.Stream(self.device)

@@ -23,11 +23,13 @@ static inline int wave_row_bytes(int n_elems, bool f32) {
   return (n_elems * (f32 ? 4 : 2) + 15) & ~15;
 }
 
-// Regions of region_bytes a block runs (the most that fit WAVE_LDS_BUDGET), or
-// -116 where one alone does not fit.
-static inline int wave_regions_per_block(int region_bytes) {
-  if (region_bytes > WAVE_LDS_BUDGET) return -116;
-  return 4 * region_bytes <= WAVE_LDS_BUDGET ? 4 : 2 * region_bytes <= WAVE_LDS_BUDGET ? 2 : 1;
+// Regions of region_bytes a block runs (the most that fit WAVE_LDS_BUDGET
+// beside shared_bytes that all its waves read), or -116 where one alone does
+// not fit.
+static inline int wave_regions_per_block(int region_bytes, int shared_bytes = 0) {
+  const int room = WAVE_LDS_BUDGET - shared_bytes;
+  if (region_bytes > room) return -116;
+  return 4 * region_bytes <= room ? 4 : 2 * region_bytes <= room ? 2 : 1;
 }
 
 // Keeps the compiler from pairing the lanes' scalar fp32 operations into
