@@ -106,7 +106,8 @@ class GpuEngine:
                  weights_dtype: Optional[str] = None,
                  classic_fused: Optional[bool] = None,
                  classic_wave: Optional[bool] = None,
-                 loco_wave: Optional[bool] = None):
+                 loco_wave: Optional[bool] = None,
+                 loco_batch: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -164,6 +165,38 @@ class GpuEngine:
                 import sys
                 print(f"[engine] loco_wave: ignoring {', '.join(ignored)} from the "
                       f"config (no wave variant)", file=sys.stderr)
+            pair_rollout = eps_fp8 = split_dyn = False
+            self.rollout_mode = "episode"
+        # loco_batch (opt-in): the block-per-member whole-episode kernel whose
+        # columns are the member's eps_per_policy episodes
+        # (rollout_loco_batch.hip, fp32 MFMA), all members in one launch per
+        # generation. Per-member rows of either dtype; no pair / fp8 / split
+        # form. Never chosen by size, never a fallback.
+        if loco_batch is None:
+            loco_batch = cfg.general.get("loco_batch", False)
+        if not isinstance(loco_batch, bool):
+            raise ValueError(f"loco_batch must be true or false, got {loco_batch!r}")
+        self.loco_batch = loco_batch
+        if loco_batch:
+            if loco_wave:
+                raise ValueError("loco_batch and loco_wave select different kernels "
+                                 "for the same rollout; set one of them")
+            for flag, val in (("pair_rollout", pair_rollout), ("eps_fp8", eps_fp8),
+                              ("split_dyn", split_dyn)):
+                if val is True:
+                    raise ValueError(
+                        f"{flag}=True is not available with loco_batch=True (the batch "
+                        f"kernel runs per-member rows only)")
+            if int(cfg.general.get("steps_per_launch", None) or 1) > 1:
+                raise ValueError(
+                    "loco_batch plays the whole episode in one launch; remove "
+                    "steps_per_launch from the config or leave loco_batch off")
+            ignored = [k for k in ("pair_rollout", "eps_fp8", "split_dyn")
+                       if bool(cfg.general.get(k, False))]
+            if ignored and not self.fp32 and comm.rank == 0:
+                import sys
+                print(f"[engine] loco_batch: ignoring {', '.join(ignored)} from the "
+                      f"config (no batch variant)", file=sys.stderr)
             pair_rollout = eps_fp8 = split_dyn = False
             self.rollout_mode = "episode"
         # steps per launch in "step" mode: k>1 runs k consecutive env steps
@@ -371,6 +404,8 @@ class GpuEngine:
         self._warned_host_ranker = False
         if self.loco_wave:
             self._loco_wave_check()
+        if self.loco_batch:
+            self._loco_batch_check()
 
         # whole-episode kernel for the classic-control envs (rollout_classic.hip):
         # ONE launch per generation instead of max_steps x (forward + a dozen
@@ -443,6 +478,32 @@ class GpuEngine:
                 f"env's matrices; got state dim {env.sdim} and widths {list(self.dims)} "
                 f"(es_loco_wave_check returned {rc})")
 
+    def _loco_batch_check(self):
+        """loco_batch=True on something the kernel does not cover fails here,
+        at construction (the rule lives in es_loco_batch_check alone)."""
+        from es_pytorch_amd.envs.locomotion import SyntheticLocomotion
+        env = self.env
+        if not (self.fused and isinstance(env, SyntheticLocomotion)
+                and self.device.type == "cuda"):
+            raise ValueError(
+                f"loco_batch runs the fused locomotion path: it needs a "
+                f"SyntheticLocomotion env on a GPU and fused left on, got "
+                f"{type(env).__name__} on {self.device.type} with fused={self.fused}")
+        lib = ops.hip()
+        if not hasattr(lib, "es_loco_batch_episode"):
+            raise RuntimeError(
+                "loco_batch=True needs es_loco_batch_episode, which the loaded HIP "
+                "library does not have (an earlier revision through ES_HIP_SO?)")
+        rc = lib.es_loco_batch_check(self.dims_arr.ctypes.data, len(self.dims_arr),
+                                     self.row_stride, env.sdim, env.ac_dim,
+                                     int(env.goal_conditioned), int(self.fp32), self.eps)
+        if rc != 0:
+            raise ValueError(
+                f"loco_batch covers eps_per_policy 1..16 and shapes whose state, "
+                f"activations and moments of all episodes fit the device's LDS; got "
+                f"eps_per_policy {self.eps}, state dim {env.sdim} and widths "
+                f"{list(self.dims)} (es_loco_batch_check returned {rc})")
+
     def _classic_wave_check(self):
         """The wave kernel's own coverage, asked of the library (the rule
         lives in es_classic_wave_check alone)."""
@@ -489,7 +550,8 @@ class GpuEngine:
             path, enc = "pair", "e4m3" if self.eps_fp8 else "bf16"
         else:
             path = "split" if self.split_dyn else \
-                "loco_wave" if self.loco_wave else "fused" if self.fused else \
+                "loco_wave" if self.loco_wave else \
+                "loco_batch" if self.loco_batch else "fused" if self.fused else \
                 "classic_wave" if self.classic_wave else \
                 "classic" if self.classic_fused else "generic"
             enc = "none"
@@ -637,10 +699,12 @@ class GpuEngine:
 
     def _loco_wave_episode(self):
         """The whole episode of all B slots in ONE launch of the wave-per-slot
-        kernel; the noiseless slots read row M - 1 of self.weights."""
+        kernel (loco_batch: of the block-per-member kernel, same arguments);
+        the noiseless slots read row M - 1 of self.weights."""
         env = self.env
         goal_ptr = env.goal.data_ptr() if env.goal_conditioned else None
-        name = "es_loco_wave_episode" + ("_f32" if self.fp32 else "")
+        name = ("es_loco_batch_episode" if self.loco_batch else "es_loco_wave_episode") + \
+            ("_f32" if self.fp32 else "")
         ops.check(getattr(ops.hip(), name)(
             self.weights.data_ptr(), self.obmean.data_ptr(), self.obstd.data_ptr(),
             self.dims_arr.ctypes.data, len(self.dims_arr), self.seed_dev.data_ptr(),
@@ -748,7 +812,7 @@ class GpuEngine:
         if self.classic_fused:
             self._classic_episode()
             return
-        if self.loco_wave:
+        if self.loco_wave or self.loco_batch:
             self._loco_wave_episode()
             return
         if self.fused and self.rollout_mode == "episode":
@@ -792,8 +856,10 @@ class GpuEngine:
 
     def _rollout(self):
         body = self._loco_step if self.fused else self._step_body
-        # classic_fused, loco_wave: one launch, nothing for a hipGraph to save
-        if self.use_graph and not self.classic_fused and not self.loco_wave:
+        # classic_fused, loco_wave, loco_batch: one launch, nothing for a
+        # hipGraph to save
+        if self.use_graph and not self.classic_fused and not self.loco_wave \
+                and not self.loco_batch:
             if self._graph is None:
                 # warmup (lazy inits must happen outside capture), then capture once
                 s = torch.cuda.Stream(self.device)

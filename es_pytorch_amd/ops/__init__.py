@@ -274,6 +274,16 @@ def _bind_hip(lib):
             fn.restype = i32
         lib.es_loco_wave_check.argtypes = [p, i32, i64, i32, i32, i32, i32]
         lib.es_loco_wave_check.restype = i32
+    # block-per-member locomotion kernel for eps_per_policy > 1 (the member's
+    # episodes as matrix columns, fp32 MFMA): es_loco_wave_episode's argument
+    # list; the check is (dims, ndims, row_stride, sdim, adim, goal_flag, f32,
+    # eps) -> what a launch would return for the shapes alone
+    if hasattr(lib, "es_loco_batch_episode"):
+        for fn in (lib.es_loco_batch_episode, lib.es_loco_batch_episode_f32):
+            fn.argtypes = lib.es_loco_episode.argtypes[:-2] + [p]
+            fn.restype = i32
+        lib.es_loco_batch_check.argtypes = [p, i32, i64, i32, i32, i32, i32, i32]
+        lib.es_loco_batch_check.restype = i32
     # fp32-weights entry points: the argument lists of their bf16 counterparts
     lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
     lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes

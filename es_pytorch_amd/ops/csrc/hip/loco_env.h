@@ -1,6 +1,7 @@
 // What the locomotion rollout files share (rollout_loco.hip,
-// rollout_loco_wave.hip): the kernel arguments of one launch and the host
-// function that validates an entry point's arguments and fills them.
+// rollout_loco_wave.hip, rollout_loco_batch.hip): the kernel arguments of one
+// launch, the bookkeeping of a slot kept on chip and the host function that
+// validates an entry point's arguments and fills them.
 #pragma once
 #include "mlp_core.h"
 
@@ -29,6 +30,35 @@ struct LocoPtrs {
   const uint16_t* Am;  // bf16 state-transition matrix (S, S)
   float *alive, *rew_total, *member_steps, *behv, *mo_sum, *mo_sumsq;
 };
+
+// ---- what the whole-episode kernels that keep a slot on chip share ----------
+// (rollout_loco_wave.hip, rollout_loco_batch.hip)
+// What a step leaves in the slot's uniform registers.
+struct LocoWaveSlot {
+  float px, py, ph, gx, gy, rew_total, member_steps;
+};
+
+// loco_dyn_finish_n's bookkeeping of a live slot in its op order, computed by
+// every lane from the reduced sums; returns whether the slot fell.
+__device__ __forceinline__ bool loco_wave_book(const LocoArgs& la, LocoWaveSlot& st,
+                                               float vfwd, float vy, float h, float asq) {
+#pragma clang fp contract(off)
+  float rew;
+  if (la.goal) {
+    const float rx = st.gx - st.px;
+    const float ry = st.gy - st.py;
+    const float inv = 1.0f / (sqrtf(rx * rx + ry * ry) + 1e-6f);
+    rew = vfwd * rx * inv + vy * ry * inv - la.ctrl * asq + la.alive_bonus;
+  } else {
+    rew = vfwd - la.ctrl * asq + la.alive_bonus;
+  }
+  st.px = st.px + la.dt * vfwd;
+  st.py = st.py + la.dt * vy;
+  st.ph = h;
+  st.rew_total = st.rew_total + rew;
+  st.member_steps = st.member_steps + 1.0f;
+  return la.terminate && h < la.fall_thr;
+}
 
 // ---- host side --------------------------------------------------------------
 // Every entry point is loco_setup (validate, build the kernel arguments) and

@@ -157,33 +157,6 @@ __device__ __forceinline__ float loco_wave_decode(const LocoArgs& la, int odim, 
   return mine ? a : 0.0f;
 }
 
-// What a step leaves in the slot's uniform registers.
-struct LocoWaveSlot {
-  float px, py, ph, gx, gy, rew_total, member_steps;
-};
-
-// loco_dyn_finish_n's bookkeeping of a live slot in its op order, computed by
-// every lane from the reduced sums; returns whether the slot fell.
-__device__ __forceinline__ bool loco_wave_book(const LocoArgs& la, LocoWaveSlot& st,
-                                               float vfwd, float vy, float h, float asq) {
-#pragma clang fp contract(off)
-  float rew;
-  if (la.goal) {
-    const float rx = st.gx - st.px;
-    const float ry = st.gy - st.py;
-    const float inv = 1.0f / (sqrtf(rx * rx + ry * ry) + 1e-6f);
-    rew = vfwd * rx * inv + vy * ry * inv - la.ctrl * asq + la.alive_bonus;
-  } else {
-    rew = vfwd - la.ctrl * asq + la.alive_bonus;
-  }
-  st.px = st.px + la.dt * vfwd;
-  st.py = st.py + la.dt * vy;
-  st.ph = h;
-  st.rew_total = st.rew_total + rew;
-  st.member_steps = st.member_steps + 1.0f;
-  return la.terminate && h < la.fall_thr;
-}
-
 template <typename WT>
 __device__ __forceinline__ void loco_wave_episode_body(const LocoWaveArgs& W) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
