@@ -28,6 +28,9 @@ One rank = one GPU; per generation:
    wavefront instead of a workgroup (``rollout_classic_wave.hip``);
    ``loco_wave`` (opt-in, state and nets at most 64 wide) does the same for
    the locomotion envs, all slots in one launch (``rollout_loco_wave.hip``);
+   ``loco_wave_batch`` (opt-in, the same widths, ``eps_per_policy`` up to 16)
+   gives each member a wavefront and runs its episodes as the columns of
+   fp32 MFMA products (``rollout_loco_wave_batch.hip``);
 4. (fit+, fit-, idx) fp64 triples go through ONE RCCL all_gather over xGMI
    (replaces the replicated Alltoall, ``es.py:84-95``); ranking runs
    redundantly on every rank (reference README.md:10-12 — parameters are
@@ -107,7 +110,8 @@ class GpuEngine:
                  classic_fused: Optional[bool] = None,
                  classic_wave: Optional[bool] = None,
                  loco_wave: Optional[bool] = None,
-                 loco_batch: Optional[bool] = None):
+                 loco_batch: Optional[bool] = None,
+                 loco_wave_batch: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -139,64 +143,26 @@ class GpuEngine:
                 print(f"[engine] weights_dtype=fp32: ignoring {', '.join(ignored)} "
                       f"from the config (no fp32 variant)", file=sys.stderr)
             pair_rollout = eps_fp8 = split_dyn = False
-        # loco_wave (opt-in): the wave-per-slot whole-episode kernel for the
-        # small locomotion envs and nets (rollout_loco_wave.hip), all B slots
-        # in one launch per generation. Per-member rows of either dtype; no
-        # pair / fp8 / split form. Never chosen by size, never a fallback.
-        if loco_wave is None:
-            loco_wave = cfg.general.get("loco_wave", False)
-        if not isinstance(loco_wave, bool):
-            raise ValueError(f"loco_wave must be true or false, got {loco_wave!r}")
-        self.loco_wave = loco_wave
-        if loco_wave:
-            for flag, val in (("pair_rollout", pair_rollout), ("eps_fp8", eps_fp8),
-                              ("split_dyn", split_dyn)):
-                if val is True:
-                    raise ValueError(
-                        f"{flag}=True is not available with loco_wave=True (the wave "
-                        f"kernel runs per-member rows only)")
-            if int(cfg.general.get("steps_per_launch", None) or 1) > 1:
-                raise ValueError(
-                    "loco_wave plays the whole episode in one launch; remove "
-                    "steps_per_launch from the config or leave loco_wave off")
-            ignored = [k for k in ("pair_rollout", "eps_fp8", "split_dyn")
-                       if bool(cfg.general.get(k, False))]
-            if ignored and not self.fp32 and comm.rank == 0:
-                import sys
-                print(f"[engine] loco_wave: ignoring {', '.join(ignored)} from the "
-                      f"config (no wave variant)", file=sys.stderr)
-            pair_rollout = eps_fp8 = split_dyn = False
-            self.rollout_mode = "episode"
-        # loco_batch (opt-in): the block-per-member whole-episode kernel whose
-        # columns are the member's eps_per_policy episodes
-        # (rollout_loco_batch.hip, fp32 MFMA), all members in one launch per
-        # generation. Per-member rows of either dtype; no pair / fp8 / split
-        # form. Never chosen by size, never a fallback.
-        if loco_batch is None:
-            loco_batch = cfg.general.get("loco_batch", False)
-        if not isinstance(loco_batch, bool):
-            raise ValueError(f"loco_batch must be true or false, got {loco_batch!r}")
-        self.loco_batch = loco_batch
-        if loco_batch:
-            if loco_wave:
-                raise ValueError("loco_batch and loco_wave select different kernels "
-                                 "for the same rollout; set one of them")
-            for flag, val in (("pair_rollout", pair_rollout), ("eps_fp8", eps_fp8),
-                              ("split_dyn", split_dyn)):
-                if val is True:
-                    raise ValueError(
-                        f"{flag}=True is not available with loco_batch=True (the batch "
-                        f"kernel runs per-member rows only)")
-            if int(cfg.general.get("steps_per_launch", None) or 1) > 1:
-                raise ValueError(
-                    "loco_batch plays the whole episode in one launch; remove "
-                    "steps_per_launch from the config or leave loco_batch off")
-            ignored = [k for k in ("pair_rollout", "eps_fp8", "split_dyn")
-                       if bool(cfg.general.get(k, False))]
-            if ignored and not self.fp32 and comm.rank == 0:
-                import sys
-                print(f"[engine] loco_batch: ignoring {', '.join(ignored)} from the "
-                      f"config (no batch variant)", file=sys.stderr)
+        # Three opt-in whole-episode kernels, all slots in ONE launch per
+        # generation, per-member rows of either dtype, no pair / fp8 / split
+        # form; never chosen by size, never a fallback, mutually exclusive:
+        # loco_wave: a wave per slot, small envs and nets (rollout_loco_wave.hip);
+        # loco_batch: a block per member whose columns are its eps_per_policy
+        # episodes (rollout_loco_batch.hip, fp32 MFMA);
+        # loco_wave_batch: a wave per member, small envs and nets, its episodes
+        # as fp32 MFMA columns, activations and state in registers
+        # (rollout_loco_wave_batch.hip).
+        flags = (("pair_rollout", pair_rollout), ("eps_fp8", eps_fp8),
+                 ("split_dyn", split_dyn))
+        self.loco_wave = loco_wave = self._episode_kernel_mode(
+            cfg, comm, "loco_wave", loco_wave, "wave", flags, ())
+        self.loco_batch = loco_batch = self._episode_kernel_mode(
+            cfg, comm, "loco_batch", loco_batch, "batch", flags,
+            (("loco_wave", loco_wave),))
+        self.loco_wave_batch = loco_wave_batch = self._episode_kernel_mode(
+            cfg, comm, "loco_wave_batch", loco_wave_batch, "wave batch", flags,
+            (("loco_wave", loco_wave), ("loco_batch", loco_batch)))
+        if loco_wave or loco_batch or loco_wave_batch:
             pair_rollout = eps_fp8 = split_dyn = False
             self.rollout_mode = "episode"
         # steps per launch in "step" mode: k>1 runs k consecutive env steps
@@ -406,6 +372,8 @@ class GpuEngine:
             self._loco_wave_check()
         if self.loco_batch:
             self._loco_batch_check()
+        if self.loco_wave_batch:
+            self._loco_wave_batch_check()
 
         # whole-episode kernel for the classic-control envs (rollout_classic.hip):
         # ONE launch per generation instead of max_steps x (forward + a dozen
@@ -432,6 +400,37 @@ class GpuEngine:
             # save_mask weighting happens at reduction time
             self.cl_ob_sum = torch.zeros((self.B, D), dtype=torch.float64, device=d)
             self.cl_ob_sumsq = torch.zeros((self.B, D), dtype=torch.float64, device=d)
+
+    def _episode_kernel_mode(self, cfg, comm, name, value, word, flags, others) -> bool:
+        """Resolve one opt-in whole-episode kernel mode (the keyword beats the
+        config) and reject what it cannot be combined with: another such mode
+        in `others`, a pair / fp8 / split flag passed as True, and
+        steps_per_launch. The same flags in the config are ignored, with a note."""
+        if value is None:
+            value = cfg.general.get(name, False)
+        if not isinstance(value, bool):
+            raise ValueError(f"{name} must be true or false, got {value!r}")
+        if not value:
+            return False
+        for other, on in others:
+            if on:
+                raise ValueError(f"{name} and {other} select different kernels "
+                                 f"for the same rollout; set one of them")
+        for flag, val in flags:
+            if val is True:
+                raise ValueError(
+                    f"{flag}=True is not available with {name}=True (the {word} "
+                    f"kernel runs per-member rows only)")
+        if int(cfg.general.get("steps_per_launch", None) or 1) > 1:
+            raise ValueError(
+                f"{name} plays the whole episode in one launch; remove "
+                f"steps_per_launch from the config or leave {name} off")
+        ignored = [k for k, _ in flags if bool(cfg.general.get(k, False))]
+        if ignored and not self.fp32 and comm.rank == 0:
+            import sys
+            print(f"[engine] {name}: ignoring {', '.join(ignored)} from the "
+                  f"config (no {word} variant)", file=sys.stderr)
+        return True
 
     def _classic_check(self):
         """classic_fused=True on something the kernel does not cover fails
@@ -504,6 +503,35 @@ class GpuEngine:
                 f"eps_per_policy {self.eps}, state dim {env.sdim} and widths "
                 f"{list(self.dims)} (es_loco_batch_check returned {rc})")
 
+    def _loco_wave_batch_check(self):
+        """loco_wave_batch=True on something the kernel does not cover fails
+        here, at construction (the rule lives in es_loco_wave_batch_check
+        alone)."""
+        from es_pytorch_amd.envs.locomotion import SyntheticLocomotion
+        env = self.env
+        if not (self.fused and isinstance(env, SyntheticLocomotion)
+                and self.device.type == "cuda"):
+            raise ValueError(
+                f"loco_wave_batch runs the fused locomotion path: it needs a "
+                f"SyntheticLocomotion env on a GPU and fused left on, got "
+                f"{type(env).__name__} on {self.device.type} with fused={self.fused}")
+        lib = ops.hip()
+        if not hasattr(lib, "es_loco_wave_batch_episode"):
+            raise RuntimeError(
+                "loco_wave_batch=True needs es_loco_wave_batch_episode, which the loaded "
+                "HIP library does not have (an earlier revision through ES_HIP_SO?)")
+        rc = lib.es_loco_wave_batch_check(self.dims_arr.ctypes.data, len(self.dims_arr),
+                                          self.row_stride, env.sdim, env.ac_dim,
+                                          int(env.goal_conditioned), int(self.fp32),
+                                          self.eps)
+        if rc != 0:
+            raise ValueError(
+                f"loco_wave_batch covers eps_per_policy 1..16, envs whose state and "
+                f"action and nets whose layers are all at most 64 wide, and parameter "
+                f"rows that fit 64 KB of LDS beside the env's matrices; got "
+                f"eps_per_policy {self.eps}, state dim {env.sdim} and widths "
+                f"{list(self.dims)} (es_loco_wave_batch_check returned {rc})")
+
     def _classic_wave_check(self):
         """The wave kernel's own coverage, asked of the library (the rule
         lives in es_classic_wave_check alone)."""
@@ -551,7 +579,9 @@ class GpuEngine:
         else:
             path = "split" if self.split_dyn else \
                 "loco_wave" if self.loco_wave else \
-                "loco_batch" if self.loco_batch else "fused" if self.fused else \
+                "loco_batch" if self.loco_batch else \
+                "loco_wave_batch" if self.loco_wave_batch else \
+                "fused" if self.fused else \
                 "classic_wave" if self.classic_wave else \
                 "classic" if self.classic_fused else "generic"
             enc = "none"
@@ -699,11 +729,14 @@ class GpuEngine:
 
     def _loco_wave_episode(self):
         """The whole episode of all B slots in ONE launch of the wave-per-slot
-        kernel (loco_batch: of the block-per-member kernel, same arguments);
+        kernel (loco_batch: of the block-per-member kernel, loco_wave_batch:
+        of the wave-per-member kernel, same arguments);
         the noiseless slots read row M - 1 of self.weights."""
         env = self.env
         goal_ptr = env.goal.data_ptr() if env.goal_conditioned else None
-        name = ("es_loco_batch_episode" if self.loco_batch else "es_loco_wave_episode") + \
+        name = ("es_loco_batch_episode" if self.loco_batch else
+                "es_loco_wave_batch_episode" if self.loco_wave_batch else
+                "es_loco_wave_episode") + \
             ("_f32" if self.fp32 else "")
         ops.check(getattr(ops.hip(), name)(
             self.weights.data_ptr(), self.obmean.data_ptr(), self.obstd.data_ptr(),
@@ -812,7 +845,7 @@ class GpuEngine:
         if self.classic_fused:
             self._classic_episode()
             return
-        if self.loco_wave or self.loco_batch:
+        if self.loco_wave or self.loco_batch or self.loco_wave_batch:
             self._loco_wave_episode()
             return
         if self.fused and self.rollout_mode == "episode":
@@ -856,10 +889,10 @@ class GpuEngine:
 
     def _rollout(self):
         body = self._loco_step if self.fused else self._step_body
-        # classic_fused, loco_wave, loco_batch: one launch, nothing for a
-        # hipGraph to save
+        # classic_fused, loco_wave, loco_batch, loco_wave_batch: one launch,
+        # nothing for a hipGraph to save
         if self.use_graph and not self.classic_fused and not self.loco_wave \
-                and not self.loco_batch:
+                and not self.loco_batch and not self.loco_wave_batch:
             if self._graph is None:
                 # warmup (lazy inits must happen outside capture), then capture once
                 s = torch.cuda.Stream(self.device)

@@ -284,6 +284,15 @@ def _bind_hip(lib):
             fn.restype = i32
         lib.es_loco_batch_check.argtypes = [p, i32, i64, i32, i32, i32, i32, i32]
         lib.es_loco_batch_check.restype = i32
+    # wave-per-member locomotion kernel for small envs and nets at
+    # eps_per_policy > 1 (the member's episodes as MFMA columns, everything in
+    # registers): es_loco_batch_episode's argument list and check
+    if hasattr(lib, "es_loco_wave_batch_episode"):
+        for fn in (lib.es_loco_wave_batch_episode, lib.es_loco_wave_batch_episode_f32):
+            fn.argtypes = lib.es_loco_episode.argtypes[:-2] + [p]
+            fn.restype = i32
+        lib.es_loco_wave_batch_check.argtypes = [p, i32, i64, i32, i32, i32, i32, i32]
+        lib.es_loco_wave_batch_check.restype = i32
     # fp32-weights entry points: the argument lists of their bf16 counterparts
     lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
     lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes

@@ -8,12 +8,17 @@ eps on the same tree:
            the config, so the engine's own gate picks pair / fp8 where it
            applies), replayed from its hipGraph
   episode  rollout_mode="episode" (es_loco_episode, a block per slot)
+  wave     loco_wave=True (es_loco_wave_episode, a wave per slot; nets at most
+           64 wide)
   batch    loco_batch=True
+  wave_batch  loco_wave_batch=True (es_loco_wave_batch_episode, a wave per
+           member, its episodes as MFMA columns; nets at most 64 wide)
 
 Method and bar are tools/loco_wave_bench.py's: same seeds, fixed parameters,
 rollouts ALTERNATE between the modes after a warm-up, each ends in a device
-synchronise; a speed claim needs the SLOWEST batch run to lead the FASTEST run
-of the other mode by more than three times the larger max - min spread.
+synchronise; a speed claim needs the SLOWEST run of the new mode (wave_batch
+where it runs, batch otherwise) to lead the FASTEST run of the other mode by
+more than three times the larger max - min spread.
 
   python tools/loco_batch_bench.py
   python tools/loco_batch_bench.py --modes default episode   # also runs on a
@@ -31,12 +36,16 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from loco_wave_bench import one_rollout  # noqa: E402
 
-ENVS = {"humanoidflagrun": "HumanoidFlagrunBulletEnv-v0", "antflagrun": "AntFlagrun-v3"}
-NETS = {"humanoidflagrun": [256, 256], "antflagrun": [64, 64]}
-MODES = ("default", "episode", "batch")
+ENVS = {"humanoidflagrun": "HumanoidFlagrunBulletEnv-v0", "antflagrun": "AntFlagrun-v3",
+        "hopper": "Hopper-v3"}
+NETS = {"humanoidflagrun": [256, 256], "antflagrun": [64, 64], "hopper": [64, 64]}
+MODES = ("default", "episode", "wave", "batch", "wave_batch")
 MODE_KW = {"default": dict(use_graph=True),
            "episode": dict(use_graph=False, rollout_mode="episode", pair_rollout=False),
-           "batch": dict(use_graph=False, loco_batch=True)}
+           "wave": dict(use_graph=False, loco_wave=True),
+           "batch": dict(use_graph=False, loco_batch=True),
+           "wave_batch": dict(use_graph=False, loco_wave_batch=True)}
+PATHS = {"wave": "loco_wave", "batch": "loco_batch", "wave_batch": "loco_wave_batch"}
 
 
 def make_engine(dev, mode, env_name, ppg, eps, layers, max_steps, seed, wdt):
@@ -66,8 +75,8 @@ def make_engine(dev, mode, env_name, ppg, eps, layers, max_steps, seed, wdt):
     nt = NoiseTable.create_shared(comm, 5_000_000, len(policy), seed=seed, device=dev)
     eng = GpuEngine(cfg, comm, policy, nt, env, np.random.RandomState(seed + 1),
                     **MODE_KW[mode])
-    if mode == "batch":
-        assert eng.numerics["path"] == "loco_batch"
+    if mode in PATHS:
+        assert eng.numerics["path"] == PATHS[mode]
     eng._upload_offsets()               # one draw: the same members every run
     eng.seed_dev.fill_(seed)
     eng.acstd_dev.fill_(0.01)
@@ -76,8 +85,10 @@ def make_engine(dev, mode, env_name, ppg, eps, layers, max_steps, seed, wdt):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--modes", nargs="+", default=list(MODES), choices=MODES)
-    p.add_argument("--envs", nargs="+", default=list(ENVS), choices=list(ENVS))
+    p.add_argument("--modes", nargs="+", default=["default", "episode", "batch"],
+                   choices=MODES)
+    p.add_argument("--envs", nargs="+", default=["humanoidflagrun", "antflagrun"],
+                   choices=list(ENVS))
     p.add_argument("--ppg", type=int, nargs="+", default=[256, 1280])
     p.add_argument("--eps", type=int, nargs="+", default=[4, 10])
     p.add_argument("--max-steps", type=int, default=1000)
@@ -92,7 +103,7 @@ def main():
     dev = torch.device("cuda", 0)
 
     rows = []
-    print(f"{'env':>16} {'ppg':>5} {'eps':>3} {'mode':>8} {'path':>16} {'rollout_s med':>13} "
+    print(f"{'env':>16} {'ppg':>5} {'eps':>3} {'mode':>10} {'path':>16} {'rollout_s med':>13} "
           f"{'min':>9} {'max':>9} {'ep_len':>7}")
     for env_key in args.envs:
         for ppg in args.ppg:
@@ -116,23 +127,24 @@ def main():
                                 "rollout_s": ro.tolist(), "rollout_s_med": float(np.median(ro)),
                                 "ep_len": float(np.mean([r[1] for r in runs[m]]))}
                     rows.append(point[m])
-                    print(f"{env_key:>16} {ppg:>5} {eps:>3} {m:>8} {path:>16} "
+                    print(f"{env_key:>16} {ppg:>5} {eps:>3} {m:>10} {path:>16} "
                           f"{np.median(ro):>13.5f} {ro.min():>9.5f} {ro.max():>9.5f} "
                           f"{point[m]['ep_len']:>7.1f}", flush=True)
-                if "batch" in point:
-                    b = np.array(point["batch"]["rollout_s"])
+                new = "wave_batch" if "wave_batch" in point else "batch"
+                if new in point:
+                    b = np.array(point[new]["rollout_s"])
                     for m in args.modes:
-                        if m == "batch":
+                        if m == new:
                             continue
                         o = np.array(point[m]["rollout_s"])
                         spread = max(o.max() - o.min(), b.max() - b.min())
                         lead = o.min() - b.max()
-                        v = {"env": env_key, "ppg": ppg, "eps": eps, "against": m,
+                        v = {"env": env_key, "ppg": ppg, "eps": eps, "new": new, "against": m,
                              "lead_s": float(lead), "spread_s": float(spread),
                              "clears_bar": bool(lead > 3 * spread),
                              "speedup_med": float(np.median(o) / np.median(b))}
                         rows.append(v)
-                        print(f"      fastest {m} - slowest batch = {lead:.5f} s, spread "
+                        print(f"      fastest {m} - slowest {new} = {lead:.5f} s, spread "
                               f"{spread:.5f} s, bar (3x spread) "
                               f"{'cleared' if v['clears_bar'] else 'NOT cleared'}, median "
                               f"rollout speed-up {v['speedup_med']:.2f}x", flush=True)
