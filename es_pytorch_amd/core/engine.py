@@ -34,7 +34,9 @@ One rank = one GPU; per generation:
 4. (fit+, fit-, idx) fp64 triples go through ONE RCCL all_gather over xGMI
    (replaces the replicated Alltoall, ``es.py:84-95``); ranking runs
    redundantly on every rank (reference README.md:10-12 — parameters are
-   never communicated);
+   never communicated); ``device_tail`` (opt-in) scores novelty and ranks on
+   the device in fp64 (``tail.hip``) instead of torch cdist + topk and the
+   host ranker;
 5. the HIP gather-GEMV reconstructs the gradient straight from the HBM noise
    table and the fused Adam/SGD kernel updates theta in place.
 
@@ -59,8 +61,9 @@ from es_pytorch_amd.nn.obstat import ObStat
 from es_pytorch_amd.nn.optimizers import SGD, Adam, Optimizer
 from es_pytorch_amd.parallel.comm import Comm
 from es_pytorch_amd.rollout.results import RewardResult
-from es_pytorch_amd.utils.novelty import novelty_batch
-from es_pytorch_amd.utils.rankers import CenteredRanker, Ranker
+from es_pytorch_amd.utils.novelty import novelty_batch, novelty_knn
+from es_pytorch_amd.utils.rankers import (CenteredRanker, DoublePositiveCenteredRanker,
+                                          MultiObjectiveRanker, Ranker)
 
 # Env steps per launch that the fp8 pair path uses when the config has no
 # `steps_per_launch`: the smallest k within the spread of the best in the
@@ -98,6 +101,17 @@ class _NoiselessResult(RewardResult):
                          np.zeros((1,) + tuple(ob_shape)), steps)
 
 
+class _Numerics(dict):
+    """GpuEngine.numerics. "tail" is stored only while device_tail is on and
+    reads as "default" otherwise, so an engine that leaves the mode off reports
+    the same items as before the mode existed."""
+
+    def __missing__(self, key):
+        if key == "tail":
+            return "default"
+        raise KeyError(key)
+
+
 class GpuEngine:
     def __init__(self, cfg, comm: Comm, policy: Policy, nt: NoiseTable, env: BatchedEnv,
                  rs: np.random.RandomState, objective: str = "reward",
@@ -111,7 +125,8 @@ class GpuEngine:
                  classic_wave: Optional[bool] = None,
                  loco_wave: Optional[bool] = None,
                  loco_batch: Optional[bool] = None,
-                 loco_wave_batch: Optional[bool] = None):
+                 loco_wave_batch: Optional[bool] = None,
+                 device_tail: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -184,6 +199,27 @@ class GpuEngine:
         self.use_graph = use_graph and self.device.type == "cuda"
         self.novelty_k = novelty_k
         self.archive: Optional[torch.Tensor] = None  # (N, 2) device tensor for ns/nsr
+        # device_tail (opt-in, independent of the rollout modes): novelty is
+        # scored by the fused kNN kernel and the fitnesses are ranked and shaped
+        # on the device in fp64 (tail.hip) instead of torch cdist + topk and the
+        # host ranker. Covers the centered and double-positive rankers, alone or
+        # inside a MultiObjectiveRanker; any other ranker is an error in step().
+        if device_tail is None:
+            device_tail = cfg.general.get("device_tail", False)
+        if not isinstance(device_tail, bool):
+            raise ValueError(f"device_tail must be true or false, got {device_tail!r}")
+        if device_tail:
+            if self.device.type != "cuda":
+                raise ValueError("device_tail=True needs a GPU engine; this one is on "
+                                 f"{self.device.type}")
+            if not hasattr(ops.hip(), "es_rank_tail"):
+                raise RuntimeError("device_tail=True needs es_novelty_knn and es_rank_tail, "
+                                   "which the loaded kernel library does not have")
+            if objective in ("ns", "nsr") and not 1 <= novelty_k <= 32:
+                raise ValueError(f"device_tail=True scores at most 32 neighbours, "
+                                 f"got novelty_k={novelty_k}")
+        self.device_tail = device_tail
+        self._rank_ws: Optional[Tuple[torch.Tensor, ...]] = None  # (rf, ri, counts)
 
         ppg = cfg.general.policies_per_gen
         assert ppg % comm.size == 0 and (ppg / comm.size) % 2 == 0, \
@@ -573,7 +609,8 @@ class GpuEngine:
     def numerics(self) -> dict:
         """Which numerics this engine evaluates the population on: weight
         precision, sigma*eps stream encoding ("none": materialized member
-        rows), rollout path and launch mode — for logs and tools."""
+        rows), rollout path and launch mode, and where novelty and ranks are
+        computed ("device": tail.hip in fp64) — for logs and tools."""
         if self.pair_rollout:
             path, enc = "pair", "e4m3" if self.eps_fp8 else "bf16"
         else:
@@ -585,8 +622,11 @@ class GpuEngine:
                 "classic_wave" if self.classic_wave else \
                 "classic" if self.classic_fused else "generic"
             enc = "none"
-        return {"weights": self.weights_dtype, "eps_encoding": enc, "path": path,
-                "rollout_mode": self.rollout_mode}
+        num = _Numerics({"weights": self.weights_dtype, "eps_encoding": enc, "path": path,
+                         "rollout_mode": self.rollout_mode})
+        if self.device_tail:
+            num["tail"] = "device"
+        return num
 
     # ------------------------------------------------------------------ ops
     def _stream(self):
@@ -966,7 +1006,11 @@ class GpuEngine:
             return behv[:, :1]
         if self.objective in ("ns", "nsr"):
             assert self.archive is not None, "set engine.archive before ns/nsr generations"
-            nov = novelty_batch(behv[:, :2], self.archive, self.novelty_k)
+            if self.device_tail:
+                # the strided last-episode rows as they lie in self.behv
+                nov = novelty_knn(behv, self.archive, self.novelty_k).float()
+            else:
+                nov = novelty_batch(behv[:, :2], self.archive, self.novelty_k)
             if self.objective == "ns":
                 return nov.unsqueeze(1)
             return torch.stack([rew, nov], dim=1)
@@ -1077,7 +1121,21 @@ class GpuEngine:
         dev_rank = (type(ranker) is CenteredRanker and O == 1
                     and self.device.type == "cuda"
                     and all_rows_dev.device.type == "cuda")
-        if dev_rank:
+        if self.device_tail:
+            # fp64 counting ranks and the shaping in tail.hip; the host only
+            # receives the mirror, after the update kernels are queued
+            rf, ri = self._device_rank(ranker, all_rows_dev, O)
+            npop = 2 * rf.numel()
+            ops.check(ops.hip().es_grad_gather(
+                self.grad.data_ptr(), self.nt.noise.data_ptr(), rf.data_ptr(),
+                ri.data_ptr(), rf.numel(), self.n, self._grad_qstd(),
+                self._stream()), "es_grad_gather")
+            self._optim_step(float(npop), float(cfg.policy.l2coeff))
+            all_rows = all_rows_dev.cpu().numpy()
+            ranker._pre_rank(all_rows[:, :O], all_rows[:, O:2 * O], all_rows[:, -1])
+            ranker.ranked_fits = rf.cpu().numpy().astype(np.float64)
+            ranker.n_fits_ranked = npop
+        elif dev_rank:
             fits_all = torch.cat([all_rows_dev[:, 0], all_rows_dev[:, 1]]).float()
             npop = fits_all.numel()
             r = torch.empty(npop, dtype=torch.float32, device=self.device)
@@ -1157,6 +1215,38 @@ class GpuEngine:
                         "env_steps": steps}
         return noiseless, gen_obstat
 
+    def _device_rank(self, ranker: Ranker, all_rows_dev: torch.Tensor,
+                     O: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(rf, ri) of the all-gathered rows by es_rank_tail, for the rankers
+        it covers; the workspace is allocated once per population size.
+        Fitnesses must be finite: NaN is not served."""
+        inner, w = ranker, 1.0
+        if type(ranker) is MultiObjectiveRanker:
+            inner, w = ranker.ranker, float(ranker.w)
+        if type(inner) not in (CenteredRanker, DoublePositiveCenteredRanker) or \
+                O != (2 if inner is not ranker else 1):
+            raise ValueError(
+                f"device_tail=True covers CenteredRanker and "
+                f"DoublePositiveCenteredRanker on one objective and a "
+                f"MultiObjectiveRanker around either on two; got "
+                f"{type(ranker).__name__} (inner {type(inner).__name__}) on "
+                f"{O} objective(s)")
+        rows = all_rows_dev.to(self.device).contiguous()
+        R = rows.shape[0]
+        if self._rank_ws is None or self._rank_ws[0].numel() != R or \
+                self._rank_ws[2].numel() != 2 * R * O:
+            self._rank_ws = (
+                torch.empty(R, dtype=torch.float32, device=self.device),
+                torch.empty(R, dtype=torch.int64, device=self.device),
+                torch.empty(2 * R * O, dtype=torch.int32, device=self.device))
+        rf, ri, counts = self._rank_ws
+        mode = 1 if type(inner) is DoublePositiveCenteredRanker else 0
+        ops.check(ops.hip().es_rank_tail(
+            rf.data_ptr(), ri.data_ptr(), counts.data_ptr(), rows.data_ptr(), R, O,
+            float(np.float32(w)), float(np.float32(1.0 - w)), mode, 0, self._stream()),
+            "es_rank_tail")
+        return rf, ri
+
     def grow_archive(self) -> float:
         """Device-resident NSR-A archive growth (reference ``nsra.py:130-135``
         + ``novelty.py:9-13``): append rank-0's noiseless behaviour to the
@@ -1167,8 +1257,13 @@ class GpuEngine:
         assert self.archive is not None, "set engine.archive first"
         b = self._member_behv()[-1][:2].double().contiguous()
         self.comm.broadcast_tensor_(b, src=0)
-        nov = float(novelty_batch(b.unsqueeze(0), self.archive,
-                                  self.novelty_k)[0].item())
+        if self.device_tail:
+            # b came from the fp32 behaviour buffer, so .float() is exact
+            nov = float(novelty_knn(b.float().unsqueeze(0), self.archive,
+                                    self.novelty_k)[0].item())
+        else:
+            nov = float(novelty_batch(b.unsqueeze(0), self.archive,
+                                      self.novelty_k)[0].item())
         self.archive = torch.cat([self.archive, b.unsqueeze(0)])
         return nov
 

@@ -293,6 +293,15 @@ def _bind_hip(lib):
             fn.restype = i32
         lib.es_loco_wave_batch_check.argtypes = [p, i32, i64, i32, i32, i32, i32, i32]
         lib.es_loco_wave_batch_check.restype = i32
+    # the tail of a generation (tail.hip). es_novelty_knn: (out_f64, behv_f32,
+    # behv_stride, B, archive_f64, N, k, stream). es_rank_tail: (rf_f32, ri_i64,
+    # counts_i32, rows_f64, R, O, w0, w1, mode, j_split, stream). -119: outside
+    # what they serve.
+    if hasattr(lib, "es_novelty_knn"):
+        lib.es_novelty_knn.argtypes = [p, p, i64, i64, p, i64, i32, p]
+        lib.es_novelty_knn.restype = i32
+        lib.es_rank_tail.argtypes = [p, p, p, p, i64, i32, f32, f32, i32, i32, p]
+        lib.es_rank_tail.restype = i32
     # fp32-weights entry points: the argument lists of their bf16 counterparts
     lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
     lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes

@@ -7,7 +7,9 @@ k nearest archive entries; new entries are produced on rank 0 and broadcast
 
 ``novelty_batch`` is the population-engine version: novelty of B behaviours
 against the archive in one torch cdist + topk (on device when the archive
-tensor lives there) — SURVEY.md K8.
+tensor lives there) — SURVEY.md K8. ``novelty_knn`` is its device counterpart
+in hand-written HIP (``ops/csrc/hip/tail.hip``): the same scores in fp64
+without the (B, N) distance matrix.
 
 
 PROVENANCE: novelty/update_archive reproduce the reference math
@@ -51,3 +53,36 @@ def novelty_batch(behaviours: torch.Tensor, archive: torch.Tensor, n: int) -> to
     k = min(n, archive.shape[0])
     smallest, _ = torch.topk(d, k, dim=1, largest=False)
     return smallest.mean(dim=1).float()
+
+
+def novelty_knn(behaviours: torch.Tensor, archive: torch.Tensor, n: int) -> torch.Tensor:
+    """Novelty of B behaviours vs an (N, 2) archive by the fused kNN kernel
+    (``es_novelty_knn``): each behaviour's n best squared distances stay in
+    registers while the archive streams through LDS, so nothing of size B x N
+    is ever written.
+
+    :param behaviours: (B, >=2) float32 CUDA tensor; columns 0 and 1 are read.
+        Rows may be strided (a view such as ``buf.view(M, eps, 3)[:, -1]``),
+        the two columns of a row are adjacent.
+    :param archive: (N, 2) contiguous float64 CUDA tensor, N >= 1
+    :param n: neighbours, 1..32; min(n, N) are averaged
+    :returns: (B,) float64 novelty scores
+    """
+    from es_pytorch_amd import ops
+    if not (behaviours.is_cuda and archive.is_cuda):
+        raise ValueError("novelty_knn runs on CUDA tensors only (novelty_batch "
+                         "is the torch version)")
+    if behaviours.dtype != torch.float32 or behaviours.dim() != 2 or \
+            behaviours.shape[1] < 2 or behaviours.stride(1) != 1:
+        raise ValueError("behaviours must be (B, >=2) float32 with adjacent columns")
+    if archive.dtype != torch.float64 or archive.dim() != 2 or archive.shape[1] != 2 \
+            or not archive.is_contiguous():
+        raise ValueError("archive must be (N, 2) contiguous float64")
+    B = behaviours.shape[0]
+    out = torch.empty(B, dtype=torch.float64, device=archive.device)
+    stride = behaviours.stride(0) if B > 1 else 0
+    ops.check(ops.hip().es_novelty_knn(
+        out.data_ptr(), behaviours.data_ptr(), stride, B, archive.data_ptr(),
+        archive.shape[0], int(n), torch.cuda.current_stream(archive.device).cuda_stream),
+        "es_novelty_knn")
+    return out
