@@ -38,7 +38,10 @@ One rank = one GPU; per generation:
    the device in fp64 (``tail.hip``) instead of torch cdist + topk and the
    host ranker;
 5. the HIP gather-GEMV reconstructs the gradient straight from the HBM noise
-   table and the fused Adam/SGD kernel updates theta in place.
+   table and the fused Adam/SGD kernel updates theta in place;
+   ``split_update`` (opt-in) does both in ONE launch that spreads the
+   population over the grid as well (``grad_update.hip``: small nets, large
+   populations).
 
 Parameter layout: device theta lives in FORWARD layout (per layer: W^T, b)
 so pheno/forward/grad are all coalesced; a precomputed permutation maps it
@@ -47,6 +50,7 @@ save/load keeps the reference's pickle format, ``policy.py:37-47``).
 """
 from __future__ import annotations
 
+import ctypes
 import time
 from typing import List, Optional, Tuple
 
@@ -102,12 +106,12 @@ class _NoiselessResult(RewardResult):
 
 
 class _Numerics(dict):
-    """GpuEngine.numerics. "tail" is stored only while device_tail is on and
-    reads as "default" otherwise, so an engine that leaves the mode off reports
+    """GpuEngine.numerics. "tail" is stored only while device_tail is on, "update"
+    only while split_update is on, and both read as "default" otherwise, so an engine that leaves the mode off reports
     the same items as before the mode existed."""
 
     def __missing__(self, key):
-        if key == "tail":
+        if key in ("tail", "update"):
             return "default"
         raise KeyError(key)
 
@@ -126,7 +130,8 @@ class GpuEngine:
                  loco_wave: Optional[bool] = None,
                  loco_batch: Optional[bool] = None,
                  loco_wave_batch: Optional[bool] = None,
-                 device_tail: Optional[bool] = None):
+                 device_tail: Optional[bool] = None,
+                 split_update: Optional[bool] = None):
         # rollout_mode: "step" = one kernel per env step for the population
         # (graph-replayed); "episode" = ONE kernel per generation, each block
         # runs its member's whole episode (members are mutually independent,
@@ -220,6 +225,24 @@ class GpuEngine:
                                  f"got novelty_k={novelty_k}")
         self.device_tail = device_tail
         self._rank_ws: Optional[Tuple[torch.Tensor, ...]] = None  # (rf, ri, counts)
+        # split_update (opt-in, independent of the rollout modes and of
+        # device_tail): the gradient gather and the Adam/SGD step run as ONE
+        # launch whose grid also splits the population (grad_update.hip)
+        # instead of es_grad_gather then es_adam_step / es_sgd_step. Never
+        # chosen by size, never a fallback.
+        if split_update is None:
+            split_update = cfg.general.get("split_update", False)
+        if not isinstance(split_update, bool):
+            raise ValueError(f"split_update must be true or false, got {split_update!r}")
+        if split_update:
+            if self.device.type != "cuda":
+                raise ValueError("split_update=True needs a GPU engine; this one is on "
+                                 f"{self.device.type}")
+            if not hasattr(ops.hip(), "es_grad_update"):
+                raise RuntimeError("split_update=True needs es_grad_update, which the "
+                                   "loaded kernel library does not have")
+        self.split_update = split_update
+        self._update_ws = None  # (n_pop, partials, ticket)
 
         ppg = cfg.general.policies_per_gen
         assert ppg % comm.size == 0 and (ppg / comm.size) % 2 == 0, \
@@ -626,6 +649,8 @@ class GpuEngine:
                          "rollout_mode": self.rollout_mode})
         if self.device_tail:
             num["tail"] = "device"
+        if self.split_update:
+            num["update"] = "split"
         return num
 
     # ------------------------------------------------------------------ ops
@@ -1126,11 +1151,7 @@ class GpuEngine:
             # receives the mirror, after the update kernels are queued
             rf, ri = self._device_rank(ranker, all_rows_dev, O)
             npop = 2 * rf.numel()
-            ops.check(ops.hip().es_grad_gather(
-                self.grad.data_ptr(), self.nt.noise.data_ptr(), rf.data_ptr(),
-                ri.data_ptr(), rf.numel(), self.n, self._grad_qstd(),
-                self._stream()), "es_grad_gather")
-            self._optim_step(float(npop), float(cfg.policy.l2coeff))
+            self._grad_update(rf, ri, float(npop), float(cfg.policy.l2coeff))
             all_rows = all_rows_dev.cpu().numpy()
             ranker._pre_rank(all_rows[:, :O], all_rows[:, O:2 * O], all_rows[:, -1])
             ranker.ranked_fits = rf.cpu().numpy().astype(np.float64)
@@ -1144,11 +1165,7 @@ class GpuEngine:
             y = r / (npop - 1) - 0.5
             rf = (y[:npop // 2] - y[npop // 2:]).contiguous()
             ri = all_rows_dev[:, 2].long().contiguous()
-            ops.check(ops.hip().es_grad_gather(
-                self.grad.data_ptr(), self.nt.noise.data_ptr(), rf.data_ptr(),
-                ri.data_ptr(), rf.numel(), self.n, self._grad_qstd(),
-                self._stream()), "es_grad_gather")
-            self._optim_step(float(npop), float(cfg.policy.l2coeff))
+            self._grad_update(rf, ri, float(npop), float(cfg.policy.l2coeff))
             # host mirror (for reporters and the entry scripts' heuristics)
             # overlaps the update kernels above
             all_rows = all_rows_dev.cpu().numpy()
@@ -1172,11 +1189,8 @@ class GpuEngine:
                                                        dtype=np.float32)).to(self.device)
             ri = torch.from_numpy(np.ascontiguousarray(ranker.noise_inds,
                                                        dtype=np.int64)).to(self.device)
-            ops.check(ops.hip().es_grad_gather(
-                self.grad.data_ptr(), self.nt.noise.data_ptr(), rf.data_ptr(),
-                ri.data_ptr(), rf.numel(), self.n, self._grad_qstd(),
-                self._stream()), "es_grad_gather")
-            self._optim_step(float(ranker.n_fits_ranked), float(cfg.policy.l2coeff))
+            self._grad_update(rf, ri, float(ranker.n_fits_ranked),
+                              float(cfg.policy.l2coeff))
         self.sync_host(light=True)
         pos, neg = all_rows[:, :O], all_rows[:, O:2 * O]
         t4 = time.perf_counter()
@@ -1275,6 +1289,46 @@ class GpuEngine:
         self.offsets[self.pairs:2 * self.pairs].copy_(self.offsets[:self.pairs])
 
     # ------------------------------------------------------------- update
+    def _grad_update(self, rf: torch.Tensor, ri: torch.Tensor, n_ranked: float, l2: float):
+        """self.grad from the ranked fits and noise indices, then the optimizer
+        step: es_grad_gather and _optim_step, or with split_update the one
+        es_grad_update launch (workspace kept per population size)."""
+        n_pop = rf.numel()
+        if not self.split_update:
+            ops.check(ops.hip().es_grad_gather(
+                self.grad.data_ptr(), self.nt.noise.data_ptr(), rf.data_ptr(),
+                ri.data_ptr(), n_pop, self.n, self._grad_qstd(),
+                self._stream()), "es_grad_gather")
+            self._optim_step(n_ranked, l2)
+            return
+        opt = self.policy.optim
+        if not isinstance(opt, (Adam, SGD)):
+            raise TypeError(f"GpuEngine supports Adam/SGD, got {type(opt).__name__}")
+        lib = ops.hip()
+        if self._update_ws is None or self._update_ws[0] != n_pop:
+            y, floats = ctypes.c_int32(0), ctypes.c_int64(0)
+            ops.check(lib.es_grad_update_plan(n_pop, self.n, ctypes.byref(y),
+                                              ctypes.byref(floats)), "es_grad_update_plan")
+            self._update_ws = (
+                n_pop,
+                torch.empty(floats.value, dtype=torch.float32, device=self.device),
+                torch.zeros((self.n + 255) // 256, dtype=torch.int32, device=self.device))
+        _, partials, ticket = self._update_ws
+        opt.t += 1
+        gscale = 1.0 / n_ranked
+        if isinstance(opt, Adam):
+            a = opt.lr * np.sqrt(1 - opt.beta2 ** opt.t) / (1 - opt.beta1 ** opt.t)
+            code, hyper = 0, (float(a), float(opt.beta1), float(opt.beta2),
+                              float(opt.epsilon))
+        else:
+            code, hyper = 1, (float(opt.lr), float(opt.momentum), 0.0, 0.0)
+        ops.check(lib.es_grad_update(
+            self.theta.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+            self.grad.data_ptr(), partials.data_ptr(), ticket.data_ptr(),
+            self.nt.noise.data_ptr(), rf.data_ptr(), ri.data_ptr(), n_pop, self.n,
+            self._grad_qstd(), code, *hyper, l2, gscale, self._stream()),
+            "es_grad_update")
+
     def _optim_step(self, n_ranked: float, l2: float):
         opt = self.policy.optim
         opt.t += 1

@@ -302,6 +302,19 @@ def _bind_hip(lib):
         lib.es_novelty_knn.restype = i32
         lib.es_rank_tail.argtypes = [p, p, p, p, i64, i32, f32, f32, i32, i32, p]
         lib.es_rank_tail.restype = i32
+    # the gather and the optimizer step in one launch, the population spread
+    # over the grid (grad_update.hip). es_grad_update: (theta, m, v, g,
+    # partials_f32, ticket_i32, table, fits, offsets, n_pop, n_params, qstd,
+    # opt 0 Adam / 1 SGD, a_or_lr, b1_or_momentum, b2, eps, l2, gscale, stream).
+    # es_grad_update_plan: (n_pop, n_params, *Y_i32, *workspace_floats_i64).
+    # -120: a size below 1 or another opt.
+    if hasattr(lib, "es_grad_update"):
+        lib.es_grad_update.argtypes = [p, p, p, p, p, p, p, p, p, i64, i64, f32, i32,
+                                       f32, f32, f32, f32, f32, f32, p]
+        lib.es_grad_update.restype = i32
+        lib.es_grad_update_plan.argtypes = [i64, i64, ctypes.POINTER(i32),
+                                            ctypes.POINTER(i64)]
+        lib.es_grad_update_plan.restype = i32
     # fp32-weights entry points: the argument lists of their bf16 counterparts
     lib.es_pheno_f32.argtypes = lib.es_pheno_bf16.argtypes
     lib.es_mlp_fwd_f32.argtypes = lib.es_mlp_fwd.argtypes
